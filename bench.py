@@ -12,10 +12,14 @@ Weak scaling: per-GPU work (2^32 nonces/step) is fixed as N grows; ``value`` is 
 of all N GPUs. ``vs_baseline`` divides by BASELINE.md's 0.99 MH/s (the reference miner.py inner loop,
 one process, measured in the survey sandbox — the reference publishes no number).
 
-The default (mine) run then also measures the second BASELINE metric in the same process on every
-rank — tx-verify/s over 2 MB blocks (8,300 signed txs each) through the native push_block path into a
-file-backed ledger — and reports it as extra keys (``verify_tx_per_s`` aggregated over ranks,
-``ecdsa_sig_per_s``, per-block commit latency); ``--verify-steps 0`` skips it. Then chain sync:
+A plain (mine) run does only that: set up, warm up, time the K steps, print the one JSON line.
+``--dump-outputs DIR`` also writes what the last timed step returned to its caller on rank 0 as
+``DIR/<name>.npy`` (``_dump_outputs``); the job is seeded, so the same arguments give the same files.
+
+``--full`` adds the side measurements to the mine run, in the same process: first the second BASELINE
+metric on every rank — tx-verify/s over 2 MB blocks (8,300 signed txs each) through the native
+push_block path into a file-backed ledger — reported as extra keys (``verify_tx_per_s`` aggregated over
+ranks, ``ecdsa_sig_per_s``, per-block commit latency); ``--verify-steps 0`` skips it. Then chain sync:
 ``sync_tx_per_s`` of one chain of 200-tx blocks replayed from /get_blocks pages (page-batched,
 ledger/pagesync.py); with N ranks the N GPUs form one cluster node syncing that chain (``--sync-steps 0``
 skips it).
@@ -48,17 +52,40 @@ def _synthetic_job(seed: int = 2026):
     return prev_hash, address, merkle
 
 
+def _dump_outputs(directory: str, step, search_res) -> None:
+    """What the last timed ``DataParallelMiner.step`` handed to its caller on this rank, as float64 ``.npy``
+    files (every value is an integer below 2^53, so float64 holds it exactly; a few KB in all):
+
+    * ``header.npy``  the agreed 108-byte block header, one value per byte (empty: no rank found one)
+    * ``nonces.npy``  this rank's exact-checked valid nonces of that sweep, in nonce-word order
+    * ``counts.npy``  [winner rank (world: none), local_hits, global_hits, searched]
+    """
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    header = step.header if step is not None and step.header is not None else b''
+    nonces = search_res.nonces if search_res is not None else []
+    counts = [] if step is None else [step.winner, step.local_hits, step.global_hits, step.searched]
+    np.save(os.path.join(directory, 'header.npy'), np.frombuffer(header, dtype=np.uint8).astype(np.float64))
+    np.save(os.path.join(directory, 'nonces.npy'), np.asarray(nonces, dtype=np.float64))
+    np.save(os.path.join(directory, 'counts.npy'), np.asarray(counts, dtype=np.float64))
+
+
 def bench_mine(args, ctx):
     from upow_amd.ops.native import gpu_available
-    from upow_amd.ops.pow import NONCE_SPACE
+    from upow_amd.ops.pow import NONCE_SPACE, search
     from upow_amd.parallel.miner_dp import DataParallelMiner
 
     device = 'gpu' if gpu_available() else 'cpu'
     count = args.nonces if args.nonces else (NONCE_SPACE if device == 'gpu' else 1 << 22)
     prev_hash, address, merkle = _synthetic_job()
     ts0 = 1_790_000_000
+    last_search = []
+
+    def search_keeping_last(*a, **kw):  # --dump-outputs: the step result carries only the count of the nonces
+        last_search[:] = [search(*a, **kw)]
+        return last_search[0]
     miner = DataParallelMiner(ctx, prev_hash, address, merkle, ts0, args.difficulty, device=device,
-                              variant=args.variant)
+                              search_fn=search_keeping_last if args.dump_outputs else search, variant=args.variant)
     for _ in range(args.warmup):
         miner.step(count)
     ctx.barrier()
@@ -66,6 +93,7 @@ def bench_mine(args, ctx):
     t0 = time.perf_counter()
     hits = 0
     winners = 0
+    r = None
     for _ in range(args.steps):
         r = miner.step(count)
         hits += r.global_hits
@@ -74,6 +102,8 @@ def bench_mine(args, ctx):
     ctx.barrier()
     dt = time.perf_counter() - t0
     dt = ctx.allreduce_max_f(dt)
+    if args.dump_outputs and ctx.is_main:
+        _dump_outputs(args.dump_outputs, r, last_search[0] if r is not None else None)
     total_hashes = count * args.steps * ctx.world
     mhs = total_hashes / dt / 1e6
     return {
@@ -232,6 +262,10 @@ def main(argv=None):
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--mode', choices=['mine', 'verify', 'sync'], default='mine')
+    ap.add_argument('--full', action='store_true',
+                    help='mine mode: after the hashrate also run the tx-verify and chain-sync side measurements')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='mine mode: write what the last timed step returned as DIR/<name>.npy (rank 0)')
     ap.add_argument('--difficulty', default='6.3')
     ap.add_argument('--nonces', type=int, default=0, help='nonce words per rank per step (default 2^32)')
     ap.add_argument('--variant', type=int, default=int(os.environ.get('UPOW_POW_VARIANT', '0')))
@@ -269,6 +303,8 @@ def main(argv=None):
     ap.add_argument('--verify-steps', type=int, default=10,
                     help='mine mode: timed 2 MB blocks of the tx-verify side measurement (0: skip; GPU only)')
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.mode != 'mine':
+        ap.error('--dump-outputs writes the mine run\'s last step (--mode mine)')
     g = str(args.governance_txs).strip()
     args.governance_txs = float(g[:-1]) / 100 if g.endswith('%') else float(g)
     g = str(args.grouped_txs).strip()
@@ -297,17 +333,18 @@ def main(argv=None):
     try:
         if args.mode == 'mine':
             out = bench_mine(args, ctx)
-            if ctx.world > 1:
+            # a plain run is the hashrate alone; the side measurements below are --full's
+            if args.full and ctx.world > 1:
                 # the multi-GPU runs report the hashrate scaling curve; the verify side metric is the 1-GPU
                 # config (BASELINE config 4), and a cluster verify here would put RCCL collectives of a second
                 # workload between the headline measurement and its one JSON line
                 out['verify_side_metrics'] = 'single-GPU runs (bench.py --mode verify --gpus N for the cluster)'
-            elif args.verify_steps > 0 and out['config']['device'] == 'gpu':
+            elif args.full and args.verify_steps > 0 and out['config']['device'] == 'gpu':
                 try:
                     out.update(_verify_side_metrics(args, ctx))
                 except Exception as e:  # the headline number stands on its own; say why the extra is missing
                     out['verify_error'] = f'{type(e).__name__}: {e}'[:300]
-            if args.sync_steps > 0 and out['config']['device'] == 'gpu':
+            if args.full and args.sync_steps > 0 and out['config']['device'] == 'gpu':
                 out.update(_guarded_side_metric(args, ctx, out))
         elif args.mode == 'verify':
             out = bench_verify(args, ctx)

@@ -5,7 +5,7 @@
 # STEPS (default: test smoke mine verify prof): any of
 #   test     pytest -m gpu (one process, per-test thread timeout)
 #   smoke    __graft_entry__.smoke()
-#   mine     bench.py (driver default: PoW MH/s + verify side metrics)
+#   mine     bench.py --full (PoW MH/s + the verify and sync side metrics)
 #   verify   bench.py --mode verify --ledger <tmp dir> (file ledger, metric 2)
 #   verifypool bench.py --mode verify --keys pool256 (file ledger, 256-key pool: the cache-friendly variant)
 #   verifygrp bench.py --mode verify --grouped-txs 10% (grouped-signature txs on the native path)
@@ -66,7 +66,7 @@ for s in $STEPS; do
         || { cat "$OUT/smoke.log"; exit 1; }
       tail -1 "$OUT/smoke.log" ;;
     mine)
-      timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" \
+      timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" \
         || { tail -20 "$OUT/bench.err"; exit 1; }
       cat "$OUT/bench.json" ;;
     verify)
@@ -139,7 +139,7 @@ for s in $STEPS; do
     launch)
       # the driver's plain command with an explicit --gpus 1 (no launcher hop) and the torchrun form
       timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-        --master-port 29534 bench.py --gpus 1 --steps 5 --warmup 1 --verify-steps 2 \
+        --master-port 29534 bench.py --gpus 1 --steps 5 --warmup 1 --full --verify-steps 2 \
         > "$OUT/bench_torchrun1.json" 2> "$OUT/bench_torchrun1.err" || { tail -20 "$OUT/bench_torchrun1.err"; exit 1; }
       grep '^{' "$OUT/bench_torchrun1.json" ;;
     coloc)
@@ -152,7 +152,7 @@ for s in $STEPS; do
       cat "$OUT/verify_mem.json" ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o pow --output-format csv \
-        -- python3 bench.py --steps 5 --warmup 1 > "$OUT/prof.log" 2>&1 || { tail -20 "$OUT/prof.log"; exit 1; }
+        -- python3 bench.py --full --steps 5 --warmup 1 > "$OUT/prof.log" 2>&1 || { tail -20 "$OUT/prof.log"; exit 1; }
       echo prof-ok ;;
     powpmc)
       # counters of the PoW search kernel (one pass per counter group; the mining bench only): VALU

@@ -1,5 +1,6 @@
 """bench.py rank launch: ``python bench.py --gpus N`` must run N ranks (driver contract), report them, and
 refuse a mismatched WORLD_SIZE. CPU ranks over gloo, the same launcher path the driver takes on a node."""
+import hashlib
 import json
 import os
 import subprocess
@@ -66,6 +67,32 @@ def test_bench_sync_and_verify_hold_txs_as_body_spans():
     rc, out, p = _run(['--mode', 'verify', '--txs', '60', '--steps', '2', '--warmup', '1'])
     assert rc == 0, p.stderr[-3000:]
     assert out['config']['block_path'] == 'native' and out['push_body_parse_ms']['native_spans'] > 0
+
+
+def test_bench_dump_outputs_same_arguments_same_files(tmp_path):
+    """--dump-outputs writes the last timed step's results as float64 .npy files; a second run with the same
+    arguments writes the same values (seeded job), and they are that sweep's: the agreed header passes the
+    PoW check and carries the first of the valid nonces. A plain run's line holds no side metric."""
+    import numpy as np
+    common = ['--gpus', '1', '--nonces', str(1 << 18), '--steps', '2', '--warmup', '1', '--difficulty', '3.5']
+    runs = []
+    for name in ('a', 'b'):
+        rc, out, p = _run([*common, '--dump-outputs', str(tmp_path / name)], env_extra={'UPOW_DISABLE_GPU': '1'})
+        assert rc == 0, p.stderr[-3000:]
+        assert out['steps'] == 2 and out['ms_per_step'] > 0 and out['metric'] == 'sha256_pow_hashrate_MH/s'
+        assert not any(k.startswith(('verify_', 'sync_')) for k in out)
+        runs.append({f: np.load(tmp_path / name / f'{f}.npy') for f in ('header', 'nonces', 'counts')})
+    a, b = runs
+    for f in a:
+        assert a[f].dtype == np.float64 and np.array_equal(a[f], b[f]), f
+    assert a['header'].shape == (108,) and len(a['nonces']) > 0
+    winner, local_hits, global_hits, searched = a['counts']
+    assert (winner, local_hits, global_hits, searched) == (0, len(a['nonces']), len(a['nonces']), 1 << 18)
+    header = bytes(a['header'].astype(np.uint8))
+    assert int.from_bytes(header[-4:], 'little') == int(a['nonces'][0])
+    from upow_amd.models.block import PowTarget
+    prev_hash = header[1:33].hex()  # v2 header: version byte, then the previous block's hash
+    assert PowTarget.from_difficulty(prev_hash, '3.5').check_hex(hashlib.sha256(header).hexdigest())
 
 
 GUARD = r'''
