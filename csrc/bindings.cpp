@@ -443,12 +443,6 @@ PYBIND11_MODULE(_native, m) {
         }
         return py::make_tuple(tags, pay, dup, fee, miss, r.n_dup);
     });
-    m.def("utxo_set_hash", [](int64_t h, uint32_t tag) {
-        std::vector<uint8_t> d;
-        uint64_t n = 0;
-        { py::gil_scoped_release rel; d = utxo_set_hash(h, tag, &n); }
-        return py::make_tuple(py::bytes(reinterpret_cast<const char*>(d.data()), d.size()), n);
-    });
     m.def("utxo_k12_snapshot", [](int64_t h, uint32_t tag) {
         py::gil_scoped_release rel;
         return utxo_k12_snapshot(h, tag);

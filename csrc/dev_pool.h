@@ -82,6 +82,7 @@ struct PooledBuf {
     T* p = nullptr;
     explicit PooledBuf(size_t n) { p = static_cast<T*>(DevPool::alloc(sizeof(T) * (n ? n : 1))); }
     ~PooledBuf() { DevPool::release(p); }
+    PooledBuf(PooledBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
     PooledBuf(const PooledBuf&) = delete;
     PooledBuf& operator=(const PooledBuf&) = delete;
 };

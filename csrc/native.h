@@ -81,7 +81,7 @@ bool p256_sign(const uint8_t d_be[32], const uint8_t digest[32], uint8_t r_le[32
 int64_t utxo_create(uint32_t log2_cap);
 void utxo_destroy(int64_t h);
 uint32_t utxo_capacity(int64_t h);
-uint64_t utxo_rehash(int64_t h, uint32_t log2_cap);  // #moved | (#no slot << 32)
+uint64_t utxo_rehash(int64_t h, uint32_t log2_cap);  // #moved | (#no slot << 32); any no slot: table unchanged
 // payload records: 80 bytes {u64 amount, u32 address length, u32 pad, address[64]} (nullptr = zeros)
 uint64_t utxo_insert(int64_t h, const uint8_t* recs, int64_t n, const uint8_t* payload);  // #full | (#duplicates << 32)
 std::vector<uint8_t> utxo_probe(int64_t h, const uint8_t* recs, int64_t n);  // tag or 0xff
@@ -111,9 +111,9 @@ struct BlockInputsOut {
 void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32_t* in_start,
                        const uint64_t* out_amount, int64_t n_out, const int32_t* out_start, int64_t n_tx,
                        uint32_t want_tag, BlockInputsOut& r);
-// K12: SHA-256 over (txid || index byte) of the entries with `tag`, sorted by (txid, index)
-std::vector<uint8_t> utxo_set_hash(int64_t h, uint32_t tag, uint64_t* count_out);
-// the (txid || index byte) message of table `tag` sorted by (txid, index): K12 without its hash tail
+// K12 = SHA-256 over (txid || index byte) of the entries with `tag`, sorted by (txid, index).
+// utxo_set_message: that message without the hash tail (the caller hashes it);
+// utxo_k12_snapshot + utxo_k12_digest: the digest of the table as it was at the snapshot, computed later
 std::vector<uint8_t> utxo_set_message(int64_t h, uint32_t tag, uint64_t* count_out);
 int64_t utxo_k12_snapshot(int64_t h, uint32_t tag);
 std::vector<uint8_t> utxo_k12_digest(int64_t id, uint64_t* count_out);

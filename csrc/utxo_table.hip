@@ -46,6 +46,13 @@ static_assert(offsetof(UtxoSlot, meta) == 32 && offsetof(UtxoSlot, pad) == 36, "
 
 enum : uint32_t { ST_EMPTY = 0, ST_FULL = 1, ST_TOMB = 2, ST_BUSY = 3 };
 
+// the meta word: state in bits 0-1, output index in bits 8-15, table tag in bits 16-23
+__device__ __forceinline__ uint32_t meta_state(uint32_t m) { return m & 3u; }
+__device__ __forceinline__ uint32_t meta_index(uint32_t m) { return (m >> 8) & 0xffu; }
+__device__ __forceinline__ uint32_t meta_tag(uint32_t m) { return (m >> 16) & 0xffu; }
+__device__ __forceinline__ uint32_t meta_full(uint32_t idx, uint32_t tag) { return ST_FULL | (idx << 8) | (tag << 16); }
+__device__ __forceinline__ uint32_t meta_tomb(uint32_t m) { return (m & ~3u) | ST_TOMB; }
+
 struct UtxoKeyRec {  // 40 bytes: txid (raw bytes), index, tag
     uint8_t txid[32];
     uint32_t index;
@@ -82,42 +89,76 @@ __device__ __forceinline__ bool key_eq(const UtxoSlot& s, const uint32_t k[8]) {
     for (int i = 0; i < 8; ++i) d |= s.k[i] ^ k[i];
     return d == 0;
 }
+// a live slot back as its key record (the inverse of load_key + meta_full)
+__device__ __forceinline__ UtxoKeyRec slot_record(const UtxoSlot& s, uint32_t m) {
+    UtxoKeyRec r;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) {
+        r.txid[4 * w] = uint8_t(s.k[w]);
+        r.txid[4 * w + 1] = uint8_t(s.k[w] >> 8);
+        r.txid[4 * w + 2] = uint8_t(s.k[w] >> 16);
+        r.txid[4 * w + 3] = uint8_t(s.k[w] >> 24);
+    }
+    r.index = meta_index(m);
+    r.tag = meta_tag(m);
+    return r;
+}
 
 // Owner fingerprint kept in the key slot (pad[0]): address bytes 1..4 (after the 42/43 parity prefix of
 // a compressed key these are x-coordinate bytes, i.e. uniformly random), so the K14 address scan can
 // reject a slot from the 48-byte key line alone and touch the 80-byte payload line only on a likely hit.
 __device__ __forceinline__ uint32_t addr_fingerprint(const uint8_t* addr) { return ld_u32(addr + 1); }
 
-// Insert: walk the probe chain to its first EMPTY slot remembering the first reusable (EMPTY or
-// tombstone) slot; a live entry with the same outpoint already in the chain is a duplicate and is not
-// inserted again (counter[1]). The remembered slot is claimed with a CAS; a lane that loses the race
-// walks the chain again. counter[0] counts entries that found no slot (table full).
-// Lanes of one launch never insert the same outpoint twice (block validation rejects duplicate inputs,
-// hence duplicate txids), so the chain walk only has to see entries published by earlier launches.
-// one entry into the table (the insert kernel's lane body, shared with the rehash): `p` = its payload or
-// nullptr, `fp` = its owner fingerprint
+// The live entry of outpoint (k, idx): walk its probe chain up to the first EMPTY slot. `slot` is NO_SLOT
+// when the outpoint is absent. ATOMIC reads the meta words with relaxed agent-scope atomic loads (the erase
+// kernel, which goes on to CAS the word it read); the read-only kernels use plain loads.
+constexpr uint32_t NO_SLOT = 0xffffffffu;
+struct LiveEntry {
+    uint32_t slot, meta;
+};
+template <bool ATOMIC>
+__device__ __forceinline__ LiveEntry find_live(const UtxoSlot* tab, uint32_t mask, const uint32_t k[8], uint32_t idx) {
+    uint32_t s = slot_hash(k, idx) & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe) {
+        const uint32_t m =
+            ATOMIC ? __hip_atomic_load(&tab[s].meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tab[s].meta;
+        const uint32_t st = meta_state(m);
+        if (st == ST_EMPTY) break;
+        if (st == ST_FULL && meta_index(m) == idx && key_eq(tab[s], k)) return {s, m};
+        s = (s + 1) & mask;
+    }
+    return {NO_SLOT, 0u};
+}
+
+// One entry into the table (the insert kernel's lane body, shared with the rehash); `p` = its payload or
+// nullptr, `fp` = its owner fingerprint. The lane walks the probe chain to its first EMPTY slot, remembering
+// the first reusable (EMPTY or tombstone) slot; a live entry with the same outpoint is a duplicate and is
+// not inserted again (counter[1]). The remembered slot is claimed with a CAS; a lane that loses the race
+// walks the chain again. counter[0] counts entries that found no slot (table full). Lanes of one launch
+// never insert the same outpoint twice (block validation rejects duplicate inputs, hence duplicate txids),
+// so the walk only has to see entries published by earlier launches.
 __device__ __forceinline__ void insert_one(UtxoSlot* __restrict__ tab, UtxoPayload* __restrict__ pay, uint32_t mask,
                                            const uint32_t k[8], uint32_t idx, uint32_t tag,
                                            const UtxoPayload* __restrict__ p, uint32_t fp,
                                            uint32_t* __restrict__ counter) {
     const uint32_t home = slot_hash(k, idx) & mask;
     for (int attempt = 0; attempt < 64; ++attempt) {
-        uint32_t s = home, free_slot = 0xffffffffu, free_meta = 0;
+        uint32_t s = home, free_slot = NO_SLOT, free_meta = 0;
         for (uint32_t probe = 0; probe <= mask; ++probe) {
             const uint32_t m = __hip_atomic_load(&tab[s].meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const uint32_t st = m & 3u;
-            if (st == ST_FULL && ((m >> 8) & 0xffu) == idx && key_eq(tab[s], k)) {
+            const uint32_t st = meta_state(m);
+            if (st == ST_FULL && meta_index(m) == idx && key_eq(tab[s], k)) {
                 atomicAdd(counter + 1, 1u);
                 return;
             }
-            if ((st == ST_EMPTY || st == ST_TOMB) && free_slot == 0xffffffffu) {
+            if ((st == ST_EMPTY || st == ST_TOMB) && free_slot == NO_SLOT) {
                 free_slot = s;
                 free_meta = m;
             }
             if (st == ST_EMPTY) break;
             s = (s + 1) & mask;
         }
-        if (free_slot == 0xffffffffu) break;
+        if (free_slot == NO_SLOT) break;
         uint32_t* mp = &tab[free_slot].meta;
         if (atomicCAS(mp, free_meta, ST_BUSY) != free_meta) continue;  // lost the race: walk again
 #pragma unroll
@@ -130,7 +171,7 @@ __device__ __forceinline__ void insert_one(UtxoSlot* __restrict__ tab, UtxoPaylo
         }
         tab[free_slot].pad[0] = fp;
         __threadfence();
-        atomicExch(mp, ST_FULL | (idx << 8) | (tag << 16));
+        atomicExch(mp, meta_full(idx, tag));
         return;
     }
     atomicAdd(counter, 1u);
@@ -158,11 +199,11 @@ __global__ __launch_bounds__(256) void utxo_migrate_kernel(const UtxoSlot* __res
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= old_cap) return;
     const uint32_t m = old_tab[s].meta;
-    if ((m & 3u) != ST_FULL) return;
+    if (meta_state(m) != ST_FULL) return;
     uint32_t k[8];
 #pragma unroll
     for (int w = 0; w < 8; ++w) k[w] = old_tab[s].k[w];
-    insert_one(tab, pay, mask, k, (m >> 8) & 0xffu, (m >> 16) & 0xffu, &old_pay[s], old_tab[s].pad[0], counter);
+    insert_one(tab, pay, mask, k, meta_index(m), meta_tag(m), &old_pay[s], old_tab[s].pad[0], counter);
     atomicAdd(counter + 2, 1u);
 }
 
@@ -174,20 +215,8 @@ __global__ __launch_bounds__(256) void utxo_probe_kernel(const UtxoSlot* __restr
     if (i >= n) return;
     uint32_t k[8];
     load_key(recs[i], k);
-    const uint32_t idx = recs[i].index & 0xffu;
-    uint32_t s = slot_hash(k, idx) & mask;
-    uint8_t res = 0xff;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        const uint32_t m = tab[s].meta;
-        const uint32_t st = m & 3u;
-        if (st == ST_EMPTY) break;
-        if (st == ST_FULL && ((m >> 8) & 0xffu) == idx && key_eq(tab[s], k)) {
-            res = uint8_t((m >> 16) & 0xffu);
-            break;
-        }
-        s = (s + 1) & mask;
-    }
-    tags_out[i] = res;
+    const LiveEntry e = find_live<false>(tab, mask, k, recs[i].index & 0xffu);
+    tags_out[i] = e.slot != NO_SLOT ? uint8_t(meta_tag(e.meta)) : 0xff;
 }
 
 // lookup = probe + payload gather (payload zeroed when absent)
@@ -200,25 +229,12 @@ __global__ __launch_bounds__(256) void utxo_lookup_kernel(const UtxoSlot* __rest
     if (i >= n) return;
     uint32_t k[8];
     load_key(recs[i], k);
-    const uint32_t idx = recs[i].index & 0xffu;
-    uint32_t s = slot_hash(k, idx) & mask;
-    uint8_t res = 0xff;
-    int64_t hit = -1;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        const uint32_t m = tab[s].meta;
-        const uint32_t st = m & 3u;
-        if (st == ST_EMPTY) break;
-        if (st == ST_FULL && ((m >> 8) & 0xffu) == idx && key_eq(tab[s], k)) {
-            res = uint8_t((m >> 16) & 0xffu);
-            hit = s;
-            break;
-        }
-        s = (s + 1) & mask;
-    }
-    tags_out[i] = res;
-    if (hit >= 0) {
-        pay_out[i] = pay[hit];
+    const LiveEntry e = find_live<false>(tab, mask, k, recs[i].index & 0xffu);
+    if (e.slot != NO_SLOT) {
+        tags_out[i] = uint8_t(meta_tag(e.meta));
+        pay_out[i] = pay[e.slot];
     } else {
+        tags_out[i] = 0xff;
         UtxoPayload z{};
         pay_out[i] = z;
     }
@@ -232,51 +248,34 @@ __global__ __launch_bounds__(256) void utxo_erase_kernel(UtxoSlot* __restrict__ 
     if (i >= n) return;
     uint32_t k[8];
     load_key(recs[i], k);
-    const uint32_t idx = recs[i].index & 0xffu, want = recs[i].tag & 0xffu;
-    uint32_t s = slot_hash(k, idx) & mask;
+    const uint32_t want = recs[i].tag & 0xffu;
+    const LiveEntry e = find_live<true>(tab, mask, k, recs[i].index & 0xffu);
     uint8_t res = 0;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        uint32_t* mp = &tab[s].meta;
-        const uint32_t m = __hip_atomic_load(mp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t st = m & 3u;
-        if (st == ST_EMPTY) break;
-        if (st == ST_FULL && ((m >> 8) & 0xffu) == idx && key_eq(tab[s], k)) {
-            if (want == 0xffu || ((m >> 16) & 0xffu) == want) {
-                if (atomicCAS(mp, m, (m & ~3u) | ST_TOMB) == m) {
-                    res = 1;
-                    atomicAdd(count, 1u);
-                }
-            }
-            break;
-        }
-        s = (s + 1) & mask;
+    if (e.slot != NO_SLOT && (want == 0xffu || meta_tag(e.meta) == want) &&
+        atomicCAS(&tab[e.slot].meta, e.meta, meta_tomb(e.meta)) == e.meta) {
+        res = 1;
+        atomicAdd(count, 1u);
     }
     erased[i] = res;
 }
 
-__global__ __launch_bounds__(256) void utxo_dump_kernel(const UtxoSlot* __restrict__ tab,
-                                                        const UtxoPayload* __restrict__ pay, uint32_t cap,
-                                                        UtxoKeyRec* __restrict__ out, UtxoPayload* __restrict__ pay_out,
-                                                        uint32_t* __restrict__ count) {
+// Collect the live entries whose tag is `tag` (ANY_TAG: every live entry) as key records, with their
+// payloads when `pay_out` is given; one atomic each, so the order is whatever the atomics give (the dump's
+// and K12's callers sort). ANY_TAG is no table tag: those are bytes.
+constexpr uint32_t ANY_TAG = 0xffffffffu;
+__global__ __launch_bounds__(256) void utxo_collect_kernel(const UtxoSlot* __restrict__ tab,
+                                                           const UtxoPayload* __restrict__ pay, uint32_t cap,
+                                                           uint32_t tag, UtxoKeyRec* __restrict__ out,
+                                                           UtxoPayload* __restrict__ pay_out,
+                                                           uint32_t* __restrict__ count) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= cap) return;
     const uint32_t m = tab[s].meta;
-    if ((m & 3u) != ST_FULL) return;
+    if (meta_state(m) != ST_FULL || (tag != ANY_TAG && meta_tag(m) != tag)) return;
     const uint32_t o = atomicAdd(count, 1u);
-    UtxoKeyRec r;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        r.txid[4 * w] = uint8_t(tab[s].k[w]);
-        r.txid[4 * w + 1] = uint8_t(tab[s].k[w] >> 8);
-        r.txid[4 * w + 2] = uint8_t(tab[s].k[w] >> 16);
-        r.txid[4 * w + 3] = uint8_t(tab[s].k[w] >> 24);
-    }
-    r.index = (m >> 8) & 0xffu;
-    r.tag = (m >> 16) & 0xffu;
-    out[o] = r;
+    out[o] = slot_record(tab[s], m);
     if (pay_out) pay_out[o] = pay[s];
 }
-
 
 // K14: outputs owned by one address (reference `database.py:909-937,1138-1205`: balance / spendable
 // outputs by address). One lane per slot streams the key metas and, for live slots whose tag is in
@@ -299,10 +298,10 @@ __global__ __launch_bounds__(256) void utxo_address_scan_kernel(const UtxoSlot* 
         // meta and fingerprint in one 16-byte load (slot bytes 32..47, 16-byte aligned)
         const uint4 mw = *reinterpret_cast<const uint4*>(&tab[s].meta);
         const uint32_t m = mw.x;
-        const uint32_t tag = (m >> 16) & 0xffu;
+        const uint32_t tag = meta_tag(m);
         // stake_sel: 0 any output, 1 only is_stake = 0 (spendable), 2 only is_stake = 1
         const uint32_t stake = tag == 0u ? (pay[s].flags & PAY_STAKE) : 0u;
-        if ((m & 3u) == ST_FULL && tag < 32u && ((tag_mask >> tag) & 1u) && mw.y == qfp &&
+        if (meta_state(m) == ST_FULL && tag < 32u && ((tag_mask >> tag) & 1u) && mw.y == qfp &&
             pay[s].addr_len == qlen && (stake_sel == 0u || (stake_sel == 1u) == (stake == 0u))) {
             const uint4* a = reinterpret_cast<const uint4*>(pay[s].addr);
             const uint4 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3];
@@ -314,17 +313,7 @@ __global__ __launch_bounds__(256) void utxo_address_scan_kernel(const UtxoSlot* 
                 amt = pay[s].amount;
                 const uint32_t o = atomicAdd(count, 1u);
                 if (o < max_out) {
-                    UtxoKeyRec r;
-#pragma unroll
-                    for (int w = 0; w < 8; ++w) {
-                        r.txid[4 * w] = uint8_t(tab[s].k[w]);
-                        r.txid[4 * w + 1] = uint8_t(tab[s].k[w] >> 8);
-                        r.txid[4 * w + 2] = uint8_t(tab[s].k[w] >> 16);
-                        r.txid[4 * w + 3] = uint8_t(tab[s].k[w] >> 24);
-                    }
-                    r.index = (m >> 8) & 0xffu;
-                    r.tag = tag;
-                    out[o] = r;
+                    out[o] = slot_record(tab[s], m);
                     pay_out[o] = pay[s];
                 }
             }
@@ -336,9 +325,14 @@ __global__ __launch_bounds__(256) void utxo_address_scan_kernel(const UtxoSlot* 
 }
 
 // ------------------------------------------------------------------------------------------------
-static void uck(hipError_t e, const char* what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+// one lane per element in 256-thread blocks on stream `st`; a failed launch throws with the kernel's name
+template <typename Kernel, typename... Args>
+static void launch(Kernel kernel, int64_t n, hipStream_t st, const char* name, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, args...);
+    stream_check(hipGetLastError(), name);
 }
+
+static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
 struct UtxoTableDev {
     int device = 0;
@@ -356,22 +350,33 @@ static UtxoTableDev& table(int64_t h) {
     auto it = g_tables.find(h);
     if (it == g_tables.end()) throw std::invalid_argument("bad utxo table handle");
     int dev = 0;
-    uck(hipGetDevice(&dev), "hipGetDevice");
-    if (dev != it->second.device) uck(hipSetDevice(it->second.device), "hipSetDevice");
+    stream_check(hipGetDevice(&dev), "hipGetDevice");
+    if (dev != it->second.device) stream_check(hipSetDevice(it->second.device), "hipSetDevice");
     return it->second;
 }
 
-int64_t utxo_create(uint32_t log2_cap) {
+// key and payload arrays of 2^log2_cap slots, zeroed on the node stream (not waited for); returns the capacity
+static uint32_t table_alloc(uint32_t log2_cap, UtxoSlot*& tab, UtxoPayload*& pay) {
     if (log2_cap < 8 || log2_cap > 31) throw std::invalid_argument("log2 capacity must be in [8, 31]");
+    const uint32_t cap = 1u << log2_cap;
+    stream_check(hipMalloc(&tab, sizeof(UtxoSlot) * size_t(cap)), "hipMalloc utxo table");
+    const hipError_t e = hipMalloc(&pay, sizeof(UtxoPayload) * size_t(cap));
+    if (e != hipSuccess) {
+        (void)hipFree(tab);
+        tab = nullptr;
+        stream_check(e, "hipMalloc utxo payload");
+    }
+    node_memset(tab, 0, sizeof(UtxoSlot) * size_t(cap), "memset utxo table");
+    node_memset(pay, 0, sizeof(UtxoPayload) * size_t(cap), "memset utxo payload");
+    return cap;
+}
+
+int64_t utxo_create(uint32_t log2_cap) {
     UtxoTableDev t;
-    uck(hipGetDevice(&t.device), "hipGetDevice");
-    t.cap = 1u << log2_cap;
-    uck(hipMalloc(&t.tab, sizeof(UtxoSlot) * size_t(t.cap)), "hipMalloc utxo table");
-    node_memset(t.tab, 0, sizeof(UtxoSlot) * size_t(t.cap), "memset utxo table");
-    uck(hipMalloc(&t.pay, sizeof(UtxoPayload) * size_t(t.cap)), "hipMalloc utxo payload");
-    node_memset(t.pay, 0, sizeof(UtxoPayload) * size_t(t.cap), "memset utxo payload");
+    stream_check(hipGetDevice(&t.device), "hipGetDevice");
+    t.cap = table_alloc(log2_cap, t.tab, t.pay);
     node_sync("utxo_create");
-    uck(hipMalloc(&t.d_counter, 2 * sizeof(uint32_t)), "hipMalloc counter");
+    stream_check(hipMalloc(&t.d_counter, 2 * sizeof(uint32_t)), "hipMalloc counter");
     std::lock_guard<std::mutex> lk(g_ut_mu);
     const int64_t h = g_next_handle++;
     g_tables[h] = t;
@@ -399,7 +404,7 @@ static bool async_collect(AsyncApply& a, uint32_t out[3]) {
     out[0] = out[1] = out[2] = 0;
     if (!a.live) return false;
     a.live = false;
-    uck(hipEventSynchronize(a.ev), "utxo async apply");
+    stream_check(hipEventSynchronize(a.ev), "utxo async apply");
     out[0] = a.res[0];
     out[1] = a.res[1];
     out[2] = a.res[2];
@@ -420,8 +425,6 @@ static void async_release(int64_t h) {  // under g_ut_mu
     g_async.erase(it);
 }
 
-static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
-
 bool utxo_apply_async(int64_t h, const std::vector<UtxoSeg>& ins, bool with_pay, const uint8_t* del, int64_t n_del,
                       uint32_t prev[3]) {
     int64_t n_ins = 0;
@@ -436,21 +439,21 @@ bool utxo_apply_async(int64_t h, const std::vector<UtxoSeg>& ins, bool with_pay,
     const size_t off_cnt = off_del + align256(size_t(n_del) * sizeof(UtxoKeyRec));
     const size_t off_st = off_cnt + 256;  // erase status bytes (device only)
     const size_t dev_need = off_st + align256(size_t(n_del));
-    if (!a.ev) uck(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming), "hipEventCreate");
+    if (!a.ev) stream_check(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming), "hipEventCreate");
     if (off_cnt + 256 > a.host_cap) {
-        if (a.host) uck(hipHostFree(a.host), "hipHostFree");  // the previous apply was collected above
+        if (a.host) stream_check(hipHostFree(a.host), "hipHostFree");  // the previous apply was collected above
         a.host = nullptr;
         a.host_cap = std::max<size_t>(off_cnt + 256, size_t(4) << 20) * 2;
-        uck(hipHostMalloc(reinterpret_cast<void**>(&a.host), a.host_cap, hipHostMallocDefault), "hipHostMalloc");
+        stream_check(hipHostMalloc(reinterpret_cast<void**>(&a.host), a.host_cap, hipHostMallocDefault), "hipHostMalloc");
     }
     if (dev_need > a.dev_cap) {
         if (a.dev) {
             node_sync("utxo async regrow");
-            uck(hipFree(a.dev), "hipFree");
+            stream_check(hipFree(a.dev), "hipFree");
         }
         a.dev = nullptr;
         a.dev_cap = std::max<size_t>(dev_need, size_t(4) << 20) * 2;
-        uck(hipMalloc(reinterpret_cast<void**>(&a.dev), a.dev_cap), "hipMalloc");
+        stream_check(hipMalloc(reinterpret_cast<void**>(&a.dev), a.dev_cap), "hipMalloc");
     }
     size_t at = 0;  // the groups land back to back: no concatenation on the caller's side
     for (const UtxoSeg& g : ins) {
@@ -461,23 +464,19 @@ bool utxo_apply_async(int64_t h, const std::vector<UtxoSeg>& ins, bool with_pay,
     }
     if (n_del) std::memcpy(a.host + off_del, del, size_t(n_del) * sizeof(UtxoKeyRec));
     hipStream_t st = node_stream();
-    uck(hipMemcpyAsync(a.dev, a.host, off_cnt, hipMemcpyHostToDevice, st), "async apply h2d");
+    stream_check(hipMemcpyAsync(a.dev, a.host, off_cnt, hipMemcpyHostToDevice, st), "async apply h2d");
     uint32_t* cnt = reinterpret_cast<uint32_t*>(a.dev + off_cnt);
-    uck(hipMemsetAsync(cnt, 0, 16, st), "async apply memset");
-    if (n_ins) {
-        hipLaunchKernelGGL(utxo_insert_kernel, dim3(int((n_ins + 255) / 256)), dim3(256), 0, st, t.tab, t.pay, t.cap - 1,
-                           reinterpret_cast<const UtxoKeyRec*>(a.dev),
-                           ins_pay ? reinterpret_cast<const UtxoPayload*>(a.dev + off_pay) : nullptr, n_ins, cnt);
-        uck(hipGetLastError(), "utxo_insert_kernel (async)");
-    }
-    if (n_del) {
-        hipLaunchKernelGGL(utxo_erase_kernel, dim3(int((n_del + 255) / 256)), dim3(256), 0, st, t.tab, t.cap - 1,
-                           reinterpret_cast<const UtxoKeyRec*>(a.dev + off_del), n_del, a.dev + off_st, cnt + 2);
-        uck(hipGetLastError(), "utxo_erase_kernel (async)");
-    }
+    stream_check(hipMemsetAsync(cnt, 0, 16, st), "async apply memset");
+    if (n_ins)
+        launch(utxo_insert_kernel, n_ins, st, "utxo_insert_kernel (async)", t.tab, t.pay, t.cap - 1,
+               reinterpret_cast<const UtxoKeyRec*>(a.dev),
+               ins_pay ? reinterpret_cast<const UtxoPayload*>(a.dev + off_pay) : nullptr, n_ins, cnt);
+    if (n_del)
+        launch(utxo_erase_kernel, n_del, st, "utxo_erase_kernel (async)", t.tab, t.cap - 1,
+               reinterpret_cast<const UtxoKeyRec*>(a.dev + off_del), n_del, a.dev + off_st, cnt + 2);
     uint32_t* res = reinterpret_cast<uint32_t*>(a.host + off_cnt);
-    uck(hipMemcpyAsync(res, cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "async apply d2h");
-    uck(hipEventRecord(a.ev, st), "hipEventRecord");
+    stream_check(hipMemcpyAsync(res, cnt, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st), "async apply d2h");
+    stream_check(hipEventRecord(a.ev, st), "hipEventRecord");
     a.res = res;
     a.live = true;
     return had;
@@ -507,37 +506,29 @@ void utxo_destroy(int64_t h) {
 
 // Rebuild the table at capacity 2^log2_cap on the device (growth, or the same size to drop tombstones): the
 // live entries move from the old arrays into fresh ones in one launch, no host round trip (the dump + host
-// re-insert it replaces moved the whole set over PCIe twice: ~0.5 GB at 5 M outpoints). Queued on the node
+// re-insert it replaced moved the whole set over PCIe twice: ~0.5 GB at 5 M outpoints). Queued on the node
 // stream behind any pending async apply, so the handle stays valid throughout. Returns (live entries moved) |
-// (entries that found no slot << 32).
+// (entries that found no slot << 32); when any found no slot the new arrays are dropped and the table stays
+// as it was.
 uint64_t utxo_rehash(int64_t h, uint32_t log2_cap) {
-    if (log2_cap < 8 || log2_cap > 31) throw std::invalid_argument("log2 capacity must be in [8, 31]");
     std::lock_guard<std::mutex> lk(g_ut_mu);
     UtxoTableDev& t = table(h);
-    const uint32_t cap = 1u << log2_cap;
     UtxoSlot* tab = nullptr;
     UtxoPayload* pay = nullptr;
-    uck(hipMalloc(&tab, sizeof(UtxoSlot) * size_t(cap)), "hipMalloc utxo table (rehash)");
-    try {
-        uck(hipMalloc(&pay, sizeof(UtxoPayload) * size_t(cap)), "hipMalloc utxo payload (rehash)");
-    } catch (...) {
-        (void)hipFree(tab);
-        throw;
-    }
-    node_memset(tab, 0, sizeof(UtxoSlot) * size_t(cap), "memset utxo table (rehash)");
-    node_memset(pay, 0, sizeof(UtxoPayload) * size_t(cap), "memset utxo payload (rehash)");
+    const uint32_t cap = table_alloc(log2_cap, tab, pay);
     PooledBuf<uint32_t> cnt(4);
     node_memset(cnt.p, 0, 4 * sizeof(uint32_t), "memset");
-    hipLaunchKernelGGL(utxo_migrate_kernel, dim3(int((t.cap + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.pay,
-                       t.cap, tab, pay, cap - 1, cnt.p);
-    uck(hipGetLastError(), "utxo_migrate_kernel");
+    launch(utxo_migrate_kernel, t.cap, node_stream(), "utxo_migrate_kernel", t.tab, t.pay, t.cap, tab, pay, cap - 1,
+           cnt.p);
     uint32_t c[4] = {0, 0, 0, 0};
-    node_d2h(c, cnt.p, sizeof c, "d2h rehash counters");  // synchronises the node stream: the old arrays are idle
-    (void)hipFree(t.tab);
-    (void)hipFree(t.pay);
-    t.tab = tab;
-    t.pay = pay;
-    t.cap = cap;
+    node_d2h(c, cnt.p, sizeof c, "d2h rehash counters");  // synchronises the node stream: both tables are idle
+    if (c[0] == 0) {
+        std::swap(t.tab, tab);
+        std::swap(t.pay, pay);
+        t.cap = cap;
+    }
+    (void)hipFree(tab);  // the old arrays, or the new ones when the rehash failed
+    (void)hipFree(pay);
     return uint64_t(c[2] - c[0]) | (uint64_t(c[0]) << 32);
 }
 
@@ -546,22 +537,19 @@ uint32_t utxo_capacity(int64_t h) {
     return table(h).cap;
 }
 
-// per-call scratch comes from the caching pool (csrc/dev_pool.h): no hipMalloc/hipFree per block
-template <typename T>
-using DevBuf = PooledBuf<T>;
+// per-call scratch (PooledBuf) comes from the caching pool (csrc/dev_pool.h): no hipMalloc/hipFree per block
 
 uint64_t utxo_insert(int64_t h, const uint8_t* recs, int64_t n, const uint8_t* payload) {
     std::lock_guard<std::mutex> lk(g_ut_mu);
     UtxoTableDev& t = table(h);
     if (n == 0) return 0;
-    DevBuf<UtxoKeyRec> d(n);
+    PooledBuf<UtxoKeyRec> d(n);
     node_h2d(d.p, recs, sizeof(UtxoKeyRec) * n, "h2d recs");
-    DevBuf<UtxoPayload> dp(payload ? n : 0);
+    PooledBuf<UtxoPayload> dp(payload ? n : 0);
     if (payload) node_h2d(dp.p, payload, sizeof(UtxoPayload) * n, "h2d payload");
     node_memset(t.d_counter, 0, 2 * sizeof(uint32_t), "memset");
-    hipLaunchKernelGGL(utxo_insert_kernel, dim3(int((n + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.pay, t.cap - 1, d.p,
-                       payload ? dp.p : nullptr, n, t.d_counter);
-    uck(hipGetLastError(), "utxo_insert_kernel");
+    launch(utxo_insert_kernel, n, node_stream(), "utxo_insert_kernel", t.tab, t.pay, t.cap - 1, d.p,
+           payload ? dp.p : nullptr, n, t.d_counter);
     uint32_t c[2] = {0, 0};
     node_d2h(c, t.d_counter, sizeof c, "d2h failed");
     return uint64_t(c[0]) | (uint64_t(c[1]) << 32);  // (table full) | (duplicates << 32)
@@ -573,13 +561,11 @@ std::vector<uint8_t> utxo_lookup(int64_t h, const uint8_t* recs, int64_t n, std:
     std::vector<uint8_t> out(static_cast<size_t>(n));
     payload_out.assign(static_cast<size_t>(n) * sizeof(UtxoPayload), 0);
     if (n == 0) return out;
-    DevBuf<UtxoKeyRec> d(n);
-    DevBuf<uint8_t> o(n);
-    DevBuf<UtxoPayload> po(n);
+    PooledBuf<UtxoKeyRec> d(n);
+    PooledBuf<uint8_t> o(n);
+    PooledBuf<UtxoPayload> po(n);
     node_h2d(d.p, recs, sizeof(UtxoKeyRec) * n, "h2d recs");
-    hipLaunchKernelGGL(utxo_lookup_kernel, dim3(int((n + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.pay, t.cap - 1, d.p, n,
-                       o.p, po.p);
-    uck(hipGetLastError(), "utxo_lookup_kernel");
+    launch(utxo_lookup_kernel, n, node_stream(), "utxo_lookup_kernel", t.tab, t.pay, t.cap - 1, d.p, n, o.p, po.p);
     node_d2h(out.data(), o.p, size_t(n), "d2h tags");
     node_d2h(payload_out.data(), po.p, payload_out.size(), "d2h payload");
     return out;
@@ -590,11 +576,10 @@ std::vector<uint8_t> utxo_probe(int64_t h, const uint8_t* recs, int64_t n) {
     UtxoTableDev& t = table(h);
     std::vector<uint8_t> out(static_cast<size_t>(n));
     if (n == 0) return out;
-    DevBuf<UtxoKeyRec> d(n);
-    DevBuf<uint8_t> o(n);
+    PooledBuf<UtxoKeyRec> d(n);
+    PooledBuf<uint8_t> o(n);
     node_h2d(d.p, recs, sizeof(UtxoKeyRec) * n, "h2d recs");
-    hipLaunchKernelGGL(utxo_probe_kernel, dim3(int((n + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.cap - 1, d.p, n, o.p);
-    uck(hipGetLastError(), "utxo_probe_kernel");
+    launch(utxo_probe_kernel, n, node_stream(), "utxo_probe_kernel", t.tab, t.cap - 1, d.p, n, o.p);
     node_d2h(out.data(), o.p, size_t(n), "d2h tags");
     return out;
 }
@@ -604,13 +589,11 @@ std::vector<uint8_t> utxo_erase(int64_t h, const uint8_t* recs, int64_t n) {
     UtxoTableDev& t = table(h);
     std::vector<uint8_t> out(static_cast<size_t>(n));
     if (n == 0) return out;
-    DevBuf<UtxoKeyRec> d(n);
-    DevBuf<uint8_t> o(n);
+    PooledBuf<UtxoKeyRec> d(n);
+    PooledBuf<uint8_t> o(n);
     node_h2d(d.p, recs, sizeof(UtxoKeyRec) * n, "h2d recs");
     node_memset(t.d_counter, 0, sizeof(uint32_t), "memset");
-    hipLaunchKernelGGL(utxo_erase_kernel, dim3(int((n + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.cap - 1, d.p, n, o.p,
-                       t.d_counter);
-    uck(hipGetLastError(), "utxo_erase_kernel");
+    launch(utxo_erase_kernel, n, node_stream(), "utxo_erase_kernel", t.tab, t.cap - 1, d.p, n, o.p, t.d_counter);
     node_d2h(out.data(), o.p, size_t(n), "d2h erased");
     return out;
 }
@@ -627,15 +610,14 @@ std::vector<uint8_t> utxo_address_scan(int64_t h, const uint8_t* addr, uint32_t 
     std::memcpy(&qfp, reinterpret_cast<const uint8_t*>(q) + 1, 4);
     // first pass sizes the output; a second pass runs only if more matches than the guess came back
     uint32_t cap_out = 4096, n = 0;
-    DevBuf<unsigned long long> dt(1);
+    PooledBuf<unsigned long long> dt(1);
     for (int pass = 0; pass < 2; ++pass) {
-        DevBuf<UtxoKeyRec> d(cap_out);
-        DevBuf<UtxoPayload> dp(cap_out);
+        PooledBuf<UtxoKeyRec> d(cap_out);
+        PooledBuf<UtxoPayload> dp(cap_out);
         node_memset(t.d_counter, 0, sizeof(uint32_t), "memset");
         node_memset(dt.p, 0, sizeof(unsigned long long), "memset");
-        hipLaunchKernelGGL(utxo_address_scan_kernel, dim3(int((t.cap + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.pay,
-                           t.cap, q[0], q[1], q[2], q[3], len, qfp, tag_mask, stake_sel, cap_out, d.p, dp.p, t.d_counter, dt.p);
-        uck(hipGetLastError(), "utxo_address_scan_kernel");
+        launch(utxo_address_scan_kernel, t.cap, node_stream(), "utxo_address_scan_kernel", t.tab, t.pay, t.cap, q[0],
+               q[1], q[2], q[3], len, qfp, tag_mask, stake_sel, cap_out, d.p, dp.p, t.d_counter, dt.p);
         node_d2h(&n, t.d_counter, sizeof(uint32_t), "d2h n");
         if (n <= cap_out) {
             unsigned long long tot = 0;
@@ -654,15 +636,20 @@ std::vector<uint8_t> utxo_address_scan(int64_t h, const uint8_t* addr, uint32_t 
     throw std::runtime_error("utxo_address_scan: table changed between passes");
 }
 
+// queue the collection of table t's entries with `tag` into out / pay_out (room for t.cap each) on the node
+// stream; `count` receives their number
+static void collect(const UtxoTableDev& t, uint32_t tag, UtxoKeyRec* out, UtxoPayload* pay_out, uint32_t* count) {
+    node_memset(count, 0, sizeof(uint32_t), "memset");
+    launch(utxo_collect_kernel, t.cap, node_stream(), "utxo_collect_kernel", t.tab, t.pay, t.cap, tag, out, pay_out,
+           count);
+}
+
 std::vector<uint8_t> utxo_dump(int64_t h, std::vector<uint8_t>* payload_out) {
     std::lock_guard<std::mutex> lk(g_ut_mu);
     UtxoTableDev& t = table(h);
-    DevBuf<UtxoKeyRec> d(t.cap);
-    DevBuf<UtxoPayload> dp(payload_out ? t.cap : 0);
-    node_memset(t.d_counter, 0, sizeof(uint32_t), "memset");
-    hipLaunchKernelGGL(utxo_dump_kernel, dim3(int((t.cap + 255) / 256)), dim3(256), 0, node_stream(), t.tab, t.pay, t.cap, d.p,
-                       payload_out ? dp.p : nullptr, t.d_counter);
-    uck(hipGetLastError(), "utxo_dump_kernel");
+    PooledBuf<UtxoKeyRec> d(t.cap);
+    PooledBuf<UtxoPayload> dp(payload_out ? t.cap : 0);
+    collect(t, ANY_TAG, d.p, payload_out ? dp.p : nullptr, t.d_counter);
     uint32_t n = 0;
     node_d2h(&n, t.d_counter, sizeof(uint32_t), "d2h n");
     std::vector<uint8_t> out(size_t(n) * sizeof(UtxoKeyRec));
@@ -758,13 +745,13 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
     {
         const size_t in_n[4] = {sizeof(UtxoKeyRec) * size_t(n_in), 8 * size_t(n_out), 4 * size_t(n_tx + 1),
                                 4 * size_t(n_tx + 1)};
-        for (int i = 0; i < 4; ++i) in_off[i + 1] = ((in_off[i] + in_n[i]) + 255) & ~size_t(255);
+        for (int i = 0; i < 4; ++i) in_off[i + 1] = align256(in_off[i] + in_n[i]);
         const size_t out_n[5] = {size_t(n_in), sizeof(UtxoPayload) * size_t(n_in), 4 * size_t(n_in),
                                  8 * size_t(n_tx), 4 * size_t(n_tx)};
-        for (int i = 0; i < 5; ++i) out_off[i + 1] = ((out_off[i] + out_n[i]) + 255) & ~size_t(255);
+        for (int i = 0; i < 5; ++i) out_off[i + 1] = align256(out_off[i] + out_n[i]);
     }
-    DevBuf<uint8_t> d_in(in_off[4]), d_outa(out_off[5]);
-    DevBuf<unsigned long long> d_scratch(scap);
+    PooledBuf<uint8_t> d_in(in_off[4]), d_outa(out_off[5]);
+    PooledBuf<unsigned long long> d_scratch(scap);
     auto* d_keys = reinterpret_cast<UtxoKeyRec*>(d_in.p + in_off[0]);
     auto* d_out = reinterpret_cast<uint64_t*>(d_in.p + in_off[1]);
     auto* d_in_start = reinterpret_cast<int32_t*>(d_in.p + in_off[2]);
@@ -785,17 +772,13 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
     put(3, out_start, 4 * size_t(n_tx + 1));
     io.h2d_issue(d_in.p, hin, in_off[4]);
     node_memset(d_scratch.p, 0, sizeof(unsigned long long) * scap, "memset scratch");
+    hipStream_t st = node_stream();
     if (n_in) {
-        const dim3 g(unsigned((n_in + 255) / 256));
-        hipLaunchKernelGGL(utxo_lookup_kernel, g, dim3(256), 0, node_stream(), t.tab, t.pay, t.cap - 1, d_keys, n_in, d_tags,
-                           d_pay);
-        uck(hipGetLastError(), "utxo_lookup_kernel");
-        hipLaunchKernelGGL(block_dup_kernel, g, dim3(256), 0, node_stream(), d_keys, n_in, d_scratch.p, scap - 1, d_dup);
-        uck(hipGetLastError(), "block_dup_kernel");
+        launch(utxo_lookup_kernel, n_in, st, "utxo_lookup_kernel", t.tab, t.pay, t.cap - 1, d_keys, n_in, d_tags, d_pay);
+        launch(block_dup_kernel, n_in, st, "block_dup_kernel", d_keys, n_in, d_scratch.p, scap - 1, d_dup);
     }
-    hipLaunchKernelGGL(block_fee_kernel, dim3(unsigned((n_tx + 255) / 256)), dim3(256), 0, node_stream(), d_tags, d_pay,
-                       d_in_start, d_out, d_out_start, n_tx, want_tag, d_fee, d_miss);
-    uck(hipGetLastError(), "block_fee_kernel");
+    launch(block_fee_kernel, n_tx, st, "block_fee_kernel", d_tags, d_pay, d_in_start, d_out, d_out_start, n_tx, want_tag,
+           d_fee, d_miss);
     const uint8_t* hout = io.d2h_arena(d_outa.p, out_off[5]);
     io.finish("block inputs");  // one sync, then each output copied once out of the pinned staging
     if (n_in) {  // (an empty numpy array's data pointer may be null)
@@ -817,30 +800,10 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
     }
 }
 
-// K12: SHA-256 over (txid || index byte) of every entry with `tag`, sorted by (txid, index).
-// Stable LSD radix sort on the device (hipCUB): index, then the txid's four 64-bit big-endian words
-// from least to most significant; the message is gathered on the device and hashed on the host
-// (Merkle–Damgard is sequential).
-__global__ __launch_bounds__(256) void set_compact_kernel(const UtxoSlot* __restrict__ tab, uint32_t cap,
-                                                          uint32_t tag, UtxoKeyRec* __restrict__ out,
-                                                          uint32_t* __restrict__ count) {
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= cap) return;
-    const uint32_t m = tab[s].meta;
-    if ((m & 3u) != ST_FULL || ((m >> 16) & 0xffu) != tag) return;
-    const uint32_t o = atomicAdd(count, 1u);
-    UtxoKeyRec r;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) {
-        r.txid[4 * w] = uint8_t(tab[s].k[w]);
-        r.txid[4 * w + 1] = uint8_t(tab[s].k[w] >> 8);
-        r.txid[4 * w + 2] = uint8_t(tab[s].k[w] >> 16);
-        r.txid[4 * w + 3] = uint8_t(tab[s].k[w] >> 24);
-    }
-    r.index = (m >> 8) & 0xffu;
-    r.tag = tag;
-    out[o] = r;
-}
+// K12: SHA-256 over (txid || index byte) of every entry with `tag`, sorted by (txid, index). The entries
+// are collected on the device (utxo_collect_kernel), sorted with a stable LSD radix sort (hipCUB): index,
+// then the txid's four 64-bit big-endian words from least to most significant; the message is gathered on
+// the device and hashed on the host (Merkle–Damgard is sequential).
 
 // column c of the sort: 0 = index, 1..4 = big-endian txid word (4 - c), gathered through perm
 __global__ __launch_bounds__(256) void sort_column_kernel(const UtxoKeyRec* __restrict__ recs,
@@ -877,45 +840,49 @@ __global__ __launch_bounds__(256) void set_message_kernel(const UtxoKeyRec* __re
     o[32] = uint8_t(r.index);
 }
 
+// The n (> 0) collected records of one table as K12's message, 33 bytes each in (txid, index) order, in a
+// device buffer; sorted and gathered on stream `st`. The sort's scratch goes back to the pool on return, so
+// the call ends with a sync of `st`.
+static PooledBuf<uint8_t> k12_sorted_message(const UtxoKeyRec* recs, uint32_t n, hipStream_t st) {
+    PooledBuf<uint32_t> perm_a(n), perm_b(n);
+    PooledBuf<uint64_t> col_a(n), col_b(n);
+    launch(iota_kernel, n, st, "iota_kernel", perm_a.p, n);
+    size_t temp_bytes = 0;
+    stream_check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, col_a.p, col_b.p, perm_a.p, perm_b.p, n, 0, 64, st),
+                 "radix sort sizing");
+    PooledBuf<uint8_t> temp(temp_bytes);
+    uint32_t* pa = perm_a.p;
+    uint32_t* pb = perm_b.p;
+    for (int c = 0; c <= 4; ++c) {  // least significant column first; radix sort is stable
+        launch(sort_column_kernel, n, st, "sort_column_kernel", recs, pa, n, c, col_a.p);
+        stream_check(hipcub::DeviceRadixSort::SortPairs(temp.p, temp_bytes, col_a.p, col_b.p, pa, pb, n, 0,
+                                                        c == 0 ? 8 : 64, st),
+                     "radix sort");
+        std::swap(pa, pb);
+    }
+    PooledBuf<uint8_t> d_msg(size_t(n) * 33);
+    launch(set_message_kernel, n, st, "set_message_kernel", recs, pa, n, d_msg.p);
+    stream_check(hipStreamSynchronize(st), "k12 sort sync");
+    return d_msg;
+}
+
 std::vector<uint8_t> utxo_set_message(int64_t h, uint32_t tag, uint64_t* count_out) {
     std::lock_guard<std::mutex> lk(g_ut_mu);
     UtxoTableDev& t = table(h);
-    DevBuf<UtxoKeyRec> recs(t.cap);
-    node_memset(t.d_counter, 0, sizeof(uint32_t), "memset");
-    hipLaunchKernelGGL(set_compact_kernel, dim3((t.cap + 255) / 256), dim3(256), 0, node_stream(), t.tab, t.cap, tag, recs.p,
-                       t.d_counter);
-    uck(hipGetLastError(), "set_compact_kernel");
+    PooledBuf<UtxoKeyRec> recs(t.cap);
+    collect(t, tag, recs.p, nullptr, t.d_counter);
     uint32_t n = 0;
     node_d2h(&n, t.d_counter, sizeof(uint32_t), "d2h n");
     if (count_out) *count_out = n;
     std::vector<uint8_t> msg(size_t(n) * 33);
     if (n) {
-        DevBuf<uint32_t> perm_a(n), perm_b(n);
-        DevBuf<uint64_t> col_a(n), col_b(n);
-        const dim3 g((n + 255) / 256);
-        hipLaunchKernelGGL(iota_kernel, g, dim3(256), 0, node_stream(), perm_a.p, n);
-        size_t temp_bytes = 0;
-        uck(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, col_a.p, col_b.p, perm_a.p, perm_b.p, n, 0, 64,
-                                               node_stream()),
-            "radix sort sizing");
-        DevBuf<uint8_t> temp(temp_bytes);
-        for (int c = 0; c <= 4; ++c) {  // least significant column first; radix sort is stable
-            hipLaunchKernelGGL(sort_column_kernel, g, dim3(256), 0, node_stream(), recs.p, perm_a.p, n, c, col_a.p);
-            uck(hipGetLastError(), "sort_column_kernel");
-            uck(hipcub::DeviceRadixSort::SortPairs(temp.p, temp_bytes, col_a.p, col_b.p, perm_a.p, perm_b.p, n,
-                                                   0, c == 0 ? 8 : 64, node_stream()),
-                "radix sort");
-            std::swap(perm_a.p, perm_b.p);
-        }
-        DevBuf<uint8_t> d_msg(size_t(n) * 33);
-        hipLaunchKernelGGL(set_message_kernel, g, dim3(256), 0, node_stream(), recs.p, perm_a.p, n, d_msg.p);
-        uck(hipGetLastError(), "set_message_kernel");
+        const PooledBuf<uint8_t> d_msg = k12_sorted_message(recs.p, n, node_stream());
         node_d2h(msg.data(), d_msg.p, msg.size(), "d2h message");
     }
     return msg;
 }
 
-// ---- K12 off the block path: the block thread takes a snapshot (one compaction launch on the node stream,
+// ---- K12 off the block path: the block thread takes a snapshot (one collection launch on the node stream,
 // so it sees exactly this block's table; no host sync), a worker thread turns it into the digest (sort and
 // gather on the aux stream, chunked D2H into pinned buffers overlapped with the host SHA-256). The next
 // block's kernels never queue behind the sort, and the 33-byte-per-UTXO message never becomes one host
@@ -939,12 +906,9 @@ int64_t utxo_k12_snapshot(int64_t h, uint32_t tag) {
         UtxoTableDev& t = table(h);
         s = std::make_unique<K12Snap>(t.cap);
         s->device = t.device;
-        node_memset(s->count.p, 0, sizeof(uint32_t), "memset k12 count");
-        hipLaunchKernelGGL(set_compact_kernel, dim3((t.cap + 255) / 256), dim3(256), 0, node_stream(), t.tab, t.cap,
-                           tag, s->recs.p, s->count.p);
-        uck(hipGetLastError(), "set_compact_kernel");
-        uck(hipEventCreateWithFlags(&s->ready, hipEventDisableTiming), "hipEventCreate");
-        uck(hipEventRecord(s->ready, node_stream()), "hipEventRecord");
+        collect(t, tag, s->recs.p, nullptr, s->count.p);
+        stream_check(hipEventCreateWithFlags(&s->ready, hipEventDisableTiming), "hipEventCreate");
+        stream_check(hipEventRecord(s->ready, node_stream()), "hipEventRecord");
     }
     std::lock_guard<std::mutex> g(g_k12_mu);
     const int64_t id = g_k12_next++;
@@ -961,57 +925,37 @@ std::vector<uint8_t> utxo_k12_digest(int64_t id, uint64_t* count_out) {
         s = std::move(it->second);
         g_k12.erase(it);
     }
-    uck(hipSetDevice(s->device), "hipSetDevice");
+    stream_check(hipSetDevice(s->device), "hipSetDevice");
     hipStream_t st = aux_stream();
-    uck(hipStreamWaitEvent(st, s->ready, 0), "hipStreamWaitEvent");
+    stream_check(hipStreamWaitEvent(st, s->ready, 0), "hipStreamWaitEvent");
     uint32_t n = 0;
-    uck(hipMemcpyAsync(&n, s->count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "d2h k12 count");
-    uck(hipStreamSynchronize(st), "k12 count sync");
+    stream_check(hipMemcpyAsync(&n, s->count.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st), "d2h k12 count");
+    stream_check(hipStreamSynchronize(st), "k12 count sync");
     if (count_out) *count_out = n;
     HostSha256 sha;
     if (n) {
-        PooledBuf<uint32_t> perm_a(n), perm_b(n);
-        PooledBuf<uint64_t> col_a(n), col_b(n);
-        const dim3 g((n + 255) / 256);
-        hipLaunchKernelGGL(iota_kernel, g, dim3(256), 0, st, perm_a.p, n);
-        size_t temp_bytes = 0;
-        uck(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, col_a.p, col_b.p, perm_a.p, perm_b.p, n, 0, 64, st),
-            "radix sort sizing");
-        PooledBuf<uint8_t> temp(temp_bytes);
-        uint32_t* pa = perm_a.p;
-        uint32_t* pb = perm_b.p;
-        for (int c = 0; c <= 4; ++c) {  // least significant column first; radix sort is stable
-            hipLaunchKernelGGL(sort_column_kernel, g, dim3(256), 0, st, s->recs.p, pa, n, c, col_a.p);
-            uck(hipGetLastError(), "sort_column_kernel");
-            uck(hipcub::DeviceRadixSort::SortPairs(temp.p, temp_bytes, col_a.p, col_b.p, pa, pb, n, 0, c == 0 ? 8 : 64,
-                                                   st),
-                "radix sort");
-            std::swap(pa, pb);
-        }
-        PooledBuf<uint8_t> d_msg(size_t(n) * 33);
-        hipLaunchKernelGGL(set_message_kernel, g, dim3(256), 0, st, s->recs.p, pa, n, d_msg.p);
-        uck(hipGetLastError(), "set_message_kernel");
+        const PooledBuf<uint8_t> d_msg = k12_sorted_message(s->recs.p, n, st);
         // two pinned staging buffers: chunk k+1 is copied while chunk k is hashed
         constexpr size_t kChunk = size_t(16) << 20;
         static uint8_t* pinned[2] = {nullptr, nullptr};
         static std::mutex pin_mu;
         std::lock_guard<std::mutex> pl(pin_mu);
         for (auto& b : pinned)
-            if (!b) uck(hipHostMalloc(reinterpret_cast<void**>(&b), kChunk, hipHostMallocDefault), "hipHostMalloc");
+            if (!b) stream_check(hipHostMalloc(reinterpret_cast<void**>(&b), kChunk, hipHostMallocDefault), "hipHostMalloc");
         hipEvent_t ev[2];
-        for (auto& e : ev) uck(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+        for (auto& e : ev) stream_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
         const size_t total = size_t(n) * 33;
         auto issue = [&](size_t off, int b) {
             const size_t len = std::min(kChunk, total - off);
-            uck(hipMemcpyAsync(pinned[b], d_msg.p + off, len, hipMemcpyDeviceToHost, st), "d2h k12 chunk");
-            uck(hipEventRecord(ev[b], st), "hipEventRecord");
+            stream_check(hipMemcpyAsync(pinned[b], d_msg.p + off, len, hipMemcpyDeviceToHost, st), "d2h k12 chunk");
+            stream_check(hipEventRecord(ev[b], st), "hipEventRecord");
             return len;
         };
         size_t off = 0;
         int b = 0;
         size_t len = issue(0, 0);
         while (len) {
-            uck(hipEventSynchronize(ev[b]), "k12 chunk sync");
+            stream_check(hipEventSynchronize(ev[b]), "k12 chunk sync");
             const size_t next = off + len;
             size_t next_len = 0;
             if (next < total) next_len = issue(next, 1 - b);
@@ -1020,20 +964,12 @@ std::vector<uint8_t> utxo_k12_digest(int64_t id, uint64_t* count_out) {
             len = next_len;
             b = 1 - b;
         }
-        uck(hipStreamSynchronize(st), "k12 sync");  // the pooled buffers may be reused after this
+        stream_check(hipStreamSynchronize(st), "k12 sync");  // the pooled buffers may be reused after this
         for (auto& e : ev) (void)hipEventDestroy(e);
     }
     (void)hipEventDestroy(s->ready);
     std::vector<uint8_t> digest(32);
     sha.final(digest.data());
-    return digest;
-}
-
-// the sequential SHA-256 tail runs without the table lock: block application is not held up by it
-std::vector<uint8_t> utxo_set_hash(int64_t h, uint32_t tag, uint64_t* count_out) {
-    const std::vector<uint8_t> msg = utxo_set_message(h, tag, count_out);
-    std::vector<uint8_t> digest(32);
-    host_sha256(msg.data(), msg.size(), digest.data());
     return digest;
 }
 

@@ -217,8 +217,8 @@ def test_duplicate_insert_is_skipped(backend, request):
 
 @pytest.mark.gpu
 def test_scan_fingerprint_after_rehash_and_tombstone_reuse(gpu):
-    """The owner fingerprint lives in the key slot: it must be rewritten when the table grows (dump +
-    re-insert) and when an insert reuses a tombstoned slot; stake flags follow the payload."""
+    """The owner fingerprint lives in the key slot: it must be carried over when the table grows (the
+    device rehash) and rewritten when an insert reuses a tombstoned slot; stake flags follow the payload."""
     from upow_amd.ledger.utxo import STAKE_EXCLUDE, STAKE_ONLY, _GpuBackend
     g = UtxoIndex(backend='gpu')
     g.be = _GpuBackend(log2_cap=8)  # 128 entries before the first rehash
@@ -332,3 +332,132 @@ def test_apply_block_gpu_async_matches_host(gpu):
     og = np.lexsort(rg.T[::-1])
     oh = np.lexsort(rh.T[::-1])
     assert (rg[og] == rh[oh]).all() and (pg[og].view(np.uint8) == ph[oh].view(np.uint8)).all()
+
+
+def _small_index(backend, request=None, log2=11):
+    """An index for a few hundred entries: on the GPU a 2^log2-slot table instead of the default 2^20."""
+    idx = UtxoIndex(backend=backend)
+    if backend == 'gpu':
+        request.getfixturevalue('gpu')
+        from upow_amd.ledger.utxo import _GpuBackend
+        idx.be = _GpuBackend(log2_cap=log2)
+    return idx
+
+
+def _k12_column_case():
+    """Outpoints whose (txid, index) order is decided by every sort column of K12 in turn: one txid with all
+    256 indices, four groups of 64 txids that differ only inside one 8-byte word of the txid (half of each
+    group in a single byte of that word), and 37 random txids: 549 entries of tag 0, in shuffled order; 50
+    entries of tag 3 over other txids."""
+    rng = random.Random(31)
+    base = rng.randbytes(32)
+    one = rng.randbytes(32).hex()
+    k0 = [(one, i) for i in range(256)]
+    for lo in (24, 16, 8, 0):
+        stem = rng.randbytes(8)
+        words = {rng.randbytes(8) for _ in range(32)}
+        words |= {stem[:j % 8] + bytes([64 + j]) + stem[j % 8 + 1:] for j in range(32)}
+        assert len(words) == 64
+        k0 += [((base[:lo] + w + base[lo + 8:]).hex(), rng.randrange(256)) for w in sorted(words)]
+    k0 += [(rng.randbytes(32).hex(), rng.randrange(256)) for _ in range(37)]
+    k3 = [(h, i) for h in (rng.randbytes(32).hex() for _ in range(10)) for i in rng.sample(range(256), 5)]
+    rng.shuffle(k0)
+    rng.shuffle(k3)
+    assert len(set(k0)) == len(k0) == 549 and len(set(k3)) == len(k3) == 50
+    return k0, k3
+
+
+def _k12_expected(keys):
+    import hashlib
+    rows = sorted((bytes.fromhex(h), i) for h, i in keys)
+    return hashlib.sha256(b''.join(t + bytes([i]) for t, i in rows)).hexdigest()
+
+
+@pytest.mark.parametrize('backend', [*HOSTS, pytest.param('gpu', marks=pytest.mark.gpu)])
+def test_k12_sort_columns_decide(backend, request):
+    """K12 of a set whose order needs every sort column (the index and each of the txid's four words), through
+    both pipelines: the synchronous message (``set_hash``) and the snapshot digested later, which must give
+    the value at the snapshot even when entries are erased before it is called."""
+    import hashlib
+    idx = _small_index(backend, request)
+    k0, k3 = _k12_column_case()
+    idx.insert(k0, 0)
+    idx.insert(k3, 3)
+    for tag, keys in ((0, k0), (3, k3)):
+        want = _k12_expected(keys)
+        assert idx.set_hash(tag) == want
+        snap = idx.k12_snapshot(tag)
+        assert idx.erase(keys[:3], tag).all()
+        assert snap() == want
+        assert idx.set_hash(tag) == _k12_expected(keys[3:])
+    empty = idx.k12_snapshot(5)
+    assert idx.set_hash(5) == empty() == hashlib.sha256(b'').hexdigest()
+
+
+@pytest.mark.gpu
+def test_gpu_table_keys_on_index_byte(gpu, request):
+    """The HBM table keys on (txid, index & 0xff), as the host tables do."""
+    idx = _small_index('gpu', request, log2=8)
+    h = _keys(1, 41)[0][0]
+    idx.insert([(h, 7)], 0, make_payload([5], [bytes([42]) + bytes(range(32))]))
+    assert idx.probe([(h, 7 + 256), (h, 8)]).tolist() == [0, MISSING]
+    tags, pay = idx.lookup([(h, 7 + 256)])
+    assert tags[0] == 0 and int(pay['amount'][0]) == 5 and int(pay['len'][0]) == 33
+    assert idx.erase([(h, 7 + 256)])[0] == 1
+    assert idx.probe([(h, 7)])[0] == MISSING and len(idx) == 0
+
+
+@pytest.mark.gpu
+def test_gpu_collect_filters_live_entries_by_tag(gpu, request):
+    """The collection kernel behind the dump and K12: every live entry with its payload, or those of one tag."""
+    g, h = _small_index('gpu', request), UtxoIndex(backend='host')
+    rng = random.Random(51)
+    keys = _keys(600, 51)
+    tags = [rng.choice((0, 3, 5)) for _ in keys]
+    pay = make_payload([rng.randrange(1, 1 << 50) for _ in keys], [bytes([42]) + rng.randbytes(32) for _ in keys])
+    for idx in (g, h):
+        for t in (0, 3, 5):
+            sel = [k for k in range(600) if tags[k] == t]
+            idx.insert([keys[k] for k in sel], t, pay[sel])
+        assert idx.erase(keys[::4]).all()
+    rg, pg = g.records_payload()
+    rh, ph = h.records_payload()
+    assert len(rg) == len(g) == 450 and rg.tobytes() == rh.tobytes() and pg.tobytes() == ph.tobytes()
+    for t in (0, 1, 3, 5):
+        live = sum(1 for k in range(600) if k % 4 and tags[k] == t)
+        assert len(g.set_message(t)) == 33 * live
+
+
+@pytest.mark.gpu
+def test_failed_rehash_keeps_the_table(gpu):
+    """A rehash into a table too small for the live set reports the entries that found no slot and leaves the
+    table as it was; a later rehash that fits moves everything."""
+    from upow_amd.ledger.utxo import sort_order
+    rng = random.Random(61)
+    recs = pack_records(_keys(300, 61), 0)
+    pay = make_payload([rng.randrange(1, 1 << 50) for _ in range(300)],
+                       [bytes([42]) + rng.randbytes(32) for _ in range(300)]).view(np.uint8)
+
+    def dump(h):
+        raw, p = gpu.utxo_dump_payload(h)
+        r, p = np.frombuffer(raw, np.uint8).reshape(-1, 40), np.frombuffer(p, np.uint8).reshape(-1, 80)
+        o = sort_order(r)
+        return r[o].tobytes(), p[o].tobytes()
+
+    h = gpu.utxo_create(9)
+    try:
+        assert gpu.utxo_insert(h, recs, pay) == (0, 0)  # 58 % load: utxo_insert does not rehash
+        before = dump(h)
+        assert len(before[0]) == 300 * 40
+        moved, failed = gpu.utxo_rehash(h, 8)
+        assert failed > 0 and moved + failed == 300
+        assert gpu.utxo_capacity(h) == 512
+        assert (np.frombuffer(gpu.utxo_probe(h, recs), np.uint8) == 0).all()
+        assert dump(h) == before
+        assert gpu.utxo_rehash(h, 10) == (300, 0)
+        assert gpu.utxo_capacity(h) == 1024
+        tags, p = gpu.utxo_lookup(h, recs)
+        assert (np.frombuffer(tags, np.uint8) == 0).all() and p == pay.tobytes()
+        assert dump(h) == before
+    finally:
+        gpu.utxo_destroy(h)

@@ -236,7 +236,7 @@ class _NativeHostBackend:
 
 
 class _GpuBackend:
-    """HBM table; grows (rehash via dump + re-insert) past 50 % load."""
+    """HBM table; past 50 % load it is rebuilt on the device (``utxo_rehash``), grown when needed."""
 
     def __init__(self, log2_cap: int = 20):
         from ..ops.native import require_gpu
