@@ -472,6 +472,21 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(py::bytes(reinterpret_cast<const char*>(o.data()), o.size()),
                               py::bytes(reinterpret_cast<const char*>(pay.data()), pay.size()), total);
     }, py::arg("h"), py::arg("addr"), py::arg("tag_mask"), py::arg("stake_sel") = 0);
+    // test hooks: (home slot u32[n], K10 fingerprint u64[n]) of key records; the table's raw 48-byte slots
+    m.def("utxo_debug_hashes", [recs_arg](py::buffer recs, uint32_t log2_cap) {
+        int64_t n; const uint8_t* p = recs_arg(recs, n);
+        py::array_t<uint32_t> home(n);
+        py::array_t<uint64_t> fp(n);
+        uint32_t* hp = home.mutable_data();
+        uint64_t* fpp = fp.mutable_data();
+        { py::gil_scoped_release rel; utxo_debug_hashes(p, n, log2_cap, hp, fpp); }
+        return py::make_tuple(home, fp);
+    }, py::arg("recs"), py::arg("log2_cap"));
+    m.def("utxo_debug_slots", [](int64_t h) {
+        std::vector<uint8_t> o;
+        { py::gil_scoped_release rel; o = utxo_debug_slots(h); }
+        return py::bytes(reinterpret_cast<const char*>(o.data()), o.size());
+    });
     m.def("utxo_dump_payload", [](int64_t h) {
         std::vector<uint8_t> o, pay;
         { py::gil_scoped_release rel; o = utxo_dump(h, &pay); }

@@ -117,6 +117,10 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
 std::vector<uint8_t> utxo_set_message(int64_t h, uint32_t tag, uint64_t* count_out);
 int64_t utxo_k12_snapshot(int64_t h, uint32_t tag);
 std::vector<uint8_t> utxo_k12_digest(int64_t id, uint64_t* count_out);
+// test hooks (not called by the node): the table's home slot at capacity 2^log2_cap and K10's fingerprint of
+// each of n key records, from the kernels' own hash functions; the table's raw 48-byte slots (cap x 48 bytes)
+void utxo_debug_hashes(const uint8_t* recs, int64_t n, uint32_t log2_cap, uint32_t* home_out, uint64_t* fp_out);
+std::vector<uint8_t> utxo_debug_slots(int64_t h);
 
 // ---------------------------------------------------------------- base58
 std::string b58encode(const uint8_t* data, size_t n);  // n <= kB58MaxInput

@@ -134,7 +134,12 @@ __device__ __forceinline__ LiveEntry find_live(const UtxoSlot* tab, uint32_t mas
 // nullptr, `fp` = its owner fingerprint. The lane walks the probe chain to its first EMPTY slot, remembering
 // the first reusable (EMPTY or tombstone) slot; a live entry with the same outpoint is a duplicate and is
 // not inserted again (counter[1]). The remembered slot is claimed with a CAS; a lane that loses the race
-// walks the chain again. counter[0] counts entries that found no slot (table full). Lanes of one launch
+// walks the chain again, for as long as its walk finds a reusable slot. A launch only ever turns reusable
+// slots into claimed ones, so each lost race is a slot gone for good and a lane loses at most capacity
+// times: the retries are bounded by progress, not by a constant (lanes of one wave that share a home slot
+// race in lockstep, one winner a round, and other waves on the same chain make whole rounds lose, so any
+// fixed count is reached by enough chosen same-home keys in one launch, on a table with room to spare).
+// counter[0] counts entries whose walk found no reusable slot (table full). Lanes of one launch
 // never insert the same outpoint twice (block validation rejects duplicate inputs, hence duplicate txids),
 // so the walk only has to see entries published by earlier launches.
 __device__ __forceinline__ void insert_one(UtxoSlot* __restrict__ tab, UtxoPayload* __restrict__ pay, uint32_t mask,
@@ -142,7 +147,7 @@ __device__ __forceinline__ void insert_one(UtxoSlot* __restrict__ tab, UtxoPaylo
                                            const UtxoPayload* __restrict__ p, uint32_t fp,
                                            uint32_t* __restrict__ counter) {
     const uint32_t home = slot_hash(k, idx) & mask;
-    for (int attempt = 0; attempt < 64; ++attempt) {
+    for (uint32_t attempt = 0; attempt <= mask; ++attempt) {
         uint32_t s = home, free_slot = NO_SLOT, free_meta = 0;
         for (uint32_t probe = 0; probe <= mask; ++probe) {
             const uint32_t m = __hip_atomic_load(&tab[s].meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -665,10 +670,16 @@ std::vector<uint8_t> utxo_dump(int64_t h, std::vector<uint8_t>* payload_out) {
 // Whole-block input pass (K7 + K10 + K11 in one round trip) and the sorted UTXO-set hash (K12).
 // ================================================================================================
 
-// K10: duplicate outpoints within a block. One 64-bit CAS per lane into a scratch table whose word
-// packs a 40-bit fingerprint of (txid, index) with the lane id of the first inserter; a lane that
-// meets its own fingerprint reports that lane (dup_of = winner + 1). The host confirms candidates
-// against the full 36-byte keys, so a fingerprint collision can never fail a valid block.
+// K10: duplicate outpoints within a block. Each lane walks a scratch table (at most half full) from the slot
+// its 64-bit fingerprint of (txid, index byte) names, with one 64-bit CAS per slot; a word packs the
+// fingerprint's top 40 bits with 1 + the lane id of the lane that claimed it (so no claimed word is 0, the
+// empty slot, whatever the fingerprint). A lane that meets its own 40 bits compares its 32 txid bytes and
+// index byte with that lane's record: equal, it reports the lane (dup_of = winner + 1) and stops; different
+// (a fingerprint collision: txids are the spender's choice, and a colliding pair costs ~2^24 hashes), it
+// goes on to the next slot like after any other occupied slot, until it claims a slot or meets a true
+// duplicate. So every outpoint has exactly one claiming lane and each later copy reports it: a collision can
+// neither fail a valid block nor hide a double spend behind another outpoint. The host confirms the reported
+// pairs against the full keys once more (a cross-check; it clears nothing the kernel got right).
 __device__ __forceinline__ uint64_t outpoint_fp(const uint32_t k[8], uint32_t idx) {
     uint64_t h = (uint64_t(k[0]) << 32 | k[1]) ^ (uint64_t(k[2]) << 17) ^ (uint64_t(k[3]) * 0x9E3779B97F4A7C15ull) ^
                  (uint64_t(k[4]) << 7) ^ (uint64_t(k[5]) << 29) ^ k[6] ^ (uint64_t(k[7]) << 41) ^
@@ -679,6 +690,14 @@ __device__ __forceinline__ uint64_t outpoint_fp(const uint32_t k[8], uint32_t id
     return h;
 }
 
+// record r names the outpoint (k, idx): all 32 txid bytes and the index byte
+__device__ __forceinline__ bool same_outpoint(const UtxoKeyRec& r, const uint32_t k[8], uint32_t idx) {
+    uint32_t d = (r.index & 0xffu) ^ idx;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) d |= ld_u32(r.txid + 4 * w) ^ k[w];
+    return d == 0;
+}
+
 __global__ __launch_bounds__(256) void block_dup_kernel(const UtxoKeyRec* __restrict__ recs, int64_t n,
                                                         unsigned long long* __restrict__ scratch, uint32_t mask,
                                                         uint32_t* __restrict__ dup_of) {
@@ -686,17 +705,21 @@ __global__ __launch_bounds__(256) void block_dup_kernel(const UtxoKeyRec* __rest
     if (i >= n) return;
     uint32_t k[8];
     load_key(recs[i], k);
-    const uint64_t fp = outpoint_fp(k, recs[i].index & 0xffu);
-    const unsigned long long mine = (fp & ~0xFFFFFFull) | (uint64_t(i) & 0xFFFFFFull);
+    const uint32_t idx = recs[i].index & 0xffu;
+    const uint64_t fp = outpoint_fp(k, idx);
     const unsigned long long want = fp & ~0xFFFFFFull;
+    const unsigned long long mine = want | (uint64_t(i + 1) & 0xFFFFFFull);  // n < 2^24: lane + 1 fits, and is not 0
     uint32_t s = uint32_t(fp) & mask;
     uint32_t res = 0;
     for (uint32_t probe = 0; probe <= mask; ++probe) {
         const unsigned long long prev = atomicCAS(&scratch[s], 0ull, mine);
         if (prev == 0ull) break;  // claimed: first occurrence
         if ((prev & ~0xFFFFFFull) == want) {
-            res = uint32_t(prev & 0xFFFFFFull) + 1u;
-            break;
+            const int64_t w = int64_t(prev & 0xFFFFFFull) - 1;  // the claiming lane; records are inputs, never written
+            if (w >= 0 && w < n && same_outpoint(recs[w], k, idx)) {
+                res = uint32_t(w) + 1u;
+                break;
+            }
         }
         s = (s + 1) & mask;
     }
@@ -788,13 +811,14 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
     }
     std::memcpy(r.fee, hout + out_off[3], 8 * size_t(n_tx));
     std::memcpy(r.missing, hout + out_off[4], 4 * size_t(n_tx));
-    // exact confirmation of duplicate candidates (full 36-byte key compare)
+    // cross-check of the reported duplicates (the kernel compared the same 33 key bytes before reporting one)
     const UtxoKeyRec* kr = reinterpret_cast<const UtxoKeyRec*>(keys);
     for (int64_t i = 0; i < n_in; ++i) {
         if (!r.dup_of[i]) continue;
         const uint32_t w = r.dup_of[i] - 1;
-        if (std::memcmp(kr[i].txid, kr[w].txid, 32) != 0 || (kr[i].index & 0xffu) != (kr[w].index & 0xffu))
-            r.dup_of[i] = 0;  // fingerprint collision, not a duplicate
+        if (w >= uint64_t(n_in) || std::memcmp(kr[i].txid, kr[w].txid, 32) != 0 ||
+            (kr[i].index & 0xffu) != (kr[w].index & 0xffu))
+            r.dup_of[i] = 0;  // not a duplicate
         else
             ++r.n_dup;
     }
@@ -971,6 +995,42 @@ std::vector<uint8_t> utxo_k12_digest(int64_t id, uint64_t* count_out) {
     std::vector<uint8_t> digest(32);
     sha.final(digest.data());
     return digest;
+}
+
+// ---- test hooks: the suite engineers probe chains and K10 fingerprint collisions from the device's own hash
+// functions and checks slot layouts against the raw table. Not called by the node.
+__global__ __launch_bounds__(256) void utxo_debug_hash_kernel(const UtxoKeyRec* __restrict__ recs, int64_t n,
+                                                              uint32_t mask, uint32_t* __restrict__ home,
+                                                              uint64_t* __restrict__ fp) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t k[8];
+    load_key(recs[i], k);
+    const uint32_t idx = recs[i].index & 0xffu;
+    home[i] = slot_hash(k, idx) & mask;
+    fp[i] = outpoint_fp(k, idx);
+}
+
+void utxo_debug_hashes(const uint8_t* recs, int64_t n, uint32_t log2_cap, uint32_t* home_out, uint64_t* fp_out) {
+    if (log2_cap < 8 || log2_cap > 31) throw std::invalid_argument("log2 capacity must be in [8, 31]");
+    if (n == 0) return;
+    node_device_enter();
+    PooledBuf<UtxoKeyRec> d(n);
+    PooledBuf<uint32_t> dh(n);
+    PooledBuf<uint64_t> df(n);
+    node_h2d(d.p, recs, sizeof(UtxoKeyRec) * size_t(n), "h2d recs");
+    launch(utxo_debug_hash_kernel, n, node_stream(), "utxo_debug_hash_kernel", d.p, n, (1u << log2_cap) - 1u, dh.p,
+           df.p);
+    node_d2h(home_out, dh.p, sizeof(uint32_t) * size_t(n), "d2h homes");
+    node_d2h(fp_out, df.p, sizeof(uint64_t) * size_t(n), "d2h fingerprints");
+}
+
+std::vector<uint8_t> utxo_debug_slots(int64_t h) {
+    std::lock_guard<std::mutex> lk(g_ut_mu);
+    UtxoTableDev& t = table(h);
+    std::vector<uint8_t> out(sizeof(UtxoSlot) * size_t(t.cap));
+    node_d2h(out.data(), t.tab, out.size(), "d2h slots");  // on the node stream: behind any pending async apply
+    return out;
 }
 
 }  // namespace upow
