@@ -472,6 +472,41 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(py::bytes(reinterpret_cast<const char*>(o.data()), o.size()),
                               py::bytes(reinterpret_cast<const char*>(pay.data()), pay.size()), total);
     }, py::arg("h"), py::arg("addr"), py::arg("tag_mask"), py::arg("stake_sel") = 0);
+    // K14 for many queries in one table pass: (qidx u32[m], recs, payload, totals u64[n]); qidx numbers the
+    // caller's queries
+    m.def("utxo_address_scan_batch", [](int64_t h, py::buffer addrs, py::buffer lens, py::buffer tag_masks,
+                                        py::buffer stake_sels) {
+        py::buffer_info ba = addrs.request(), bl = lens.request(), bt = tag_masks.request(),
+                        bs = stake_sels.request();
+        auto contiguous = [](const py::buffer_info& b) {
+            py::ssize_t want = b.itemsize;
+            for (py::ssize_t d = b.ndim; d-- > 0;) {
+                if (b.shape[d] > 1 && b.strides[d] != want) return false;
+                want *= b.shape[d];
+            }
+            return true;
+        };
+        if (!contiguous(ba) || !contiguous(bl) || !contiguous(bt) || !contiguous(bs))
+            throw std::invalid_argument("query arrays must be contiguous");
+        const size_t ln = size_t(bl.size * bl.itemsize);
+        if (bl.itemsize != 4 || bt.itemsize != 4 || bs.itemsize != 4 || size_t(bt.size * bt.itemsize) != ln || size_t(bs.size * bs.itemsize) != ln ||
+            size_t(ba.size * ba.itemsize) != ln * 16)
+            throw std::invalid_argument("queries are n x 64 address bytes and three u32[n] arrays");
+        const int64_t n = int64_t(ln / 4);
+        AddressBatchOut r;
+        if (n) {
+            py::gil_scoped_release rel;
+            utxo_address_scan_batch(h, static_cast<const uint8_t*>(ba.ptr), static_cast<const uint32_t*>(bl.ptr),
+                                    static_cast<const uint32_t*>(bt.ptr), static_cast<const uint32_t*>(bs.ptr), n, r);
+        }
+        const py::ssize_t n_match = py::ssize_t(r.qidx.size()), n_query = py::ssize_t(n);
+        py::array_t<uint32_t> qidx(n_match);
+        py::array_t<uint64_t> totals(n_query);
+        if (!r.qidx.empty()) std::memcpy(qidx.mutable_data(), r.qidx.data(), r.qidx.size() * 4);
+        if (n) std::memcpy(totals.mutable_data(), r.totals.data(), size_t(n) * 8);
+        return py::make_tuple(qidx, py::bytes(reinterpret_cast<const char*>(r.recs.data()), r.recs.size()),
+                              py::bytes(reinterpret_cast<const char*>(r.payload.data()), r.payload.size()), totals);
+    }, py::arg("h"), py::arg("addrs"), py::arg("lens"), py::arg("tag_masks"), py::arg("stake_sels"));
     // test hooks: (home slot u32[n], K10 fingerprint u64[n]) of key records; the table's raw 48-byte slots
     m.def("utxo_debug_hashes", [recs_arg](py::buffer recs, uint32_t log2_cap) {
         int64_t n; const uint8_t* p = recs_arg(recs, n);

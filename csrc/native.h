@@ -97,6 +97,18 @@ std::vector<uint8_t> utxo_dump(int64_t h, std::vector<uint8_t>* payload_out);
 // K14: live outputs whose payload address equals addr[0:len] and whose tag is in tag_mask
 std::vector<uint8_t> utxo_address_scan(int64_t h, const uint8_t* addr, uint32_t len, uint32_t tag_mask,
                                        uint32_t stake_sel, std::vector<uint8_t>& payload_out, uint64_t* total_out);
+// K14 for n queries in one table pass (ceil(n / 1024) launches under one lock hold): query i is addrs[64 i ..
+// 64 i + lens[i]) with its own tag mask and stake selector. Matches come back in no particular order, each
+// with the index of the query it answers (a slot matching several queries appears once per query; exact
+// duplicate queries get equal answers); totals[i] = the amount sum of query i's matches.
+struct AddressBatchOut {
+    std::vector<uint32_t> qidx;    // per match: query index in the caller's numbering
+    std::vector<uint8_t> recs;     // per match: 40-byte key record
+    std::vector<uint8_t> payload;  // per match: 80-byte payload
+    std::vector<uint64_t> totals;  // per query
+};
+void utxo_address_scan_batch(int64_t h, const uint8_t* addrs, const uint32_t* lens, const uint32_t* tag_masks,
+                             const uint32_t* stake_sels, int64_t n, AddressBatchOut& out);
 
 // whole-block input pass: lookup (K7) + duplicate candidates (K10) + per-tx fees (K11) in one round trip
 // Outputs of the whole-block input pass, written in place (the caller's arrays: no intermediate copies)

@@ -25,7 +25,7 @@ from datetime import datetime, timedelta, timezone
 from decimal import ROUND_HALF_UP, Decimal
 from statistics import mean
 from time import perf_counter
-from typing import Any, Dict, Iterable, List, Optional, Set, Tuple, Union
+from typing import Any, Dict, Iterable, List, Optional, Sequence, Set, Tuple, Union
 
 import numpy as np
 
@@ -2890,22 +2890,35 @@ class Database:
 
     def _index_address_rows(self, address: str, stake_sel: int, check_pending: bool) -> List[Tuple[str, int, int]]:
         """(tx_hash, index, amount) of the live ``unspent_outputs`` entries owned by ``address`` (either byte
-        form), from the UTXO index (K14: one HBM scan per form on a GPU node, an owner map on the host)
+        form), from the UTXO index (K14: one HBM pass for both forms on a GPU node, an owner map on the host)
         in canonical (tx_hash, index) order. The reference's ``address = ANY($1)`` over unspent_outputs
         (database.py:909-937) has no defined row order; the index answers at the commit point, without
         waiting for the SQL materialiser and without an address B-tree to maintain per block."""
+        return self._index_address_rows_many([address], stake_sel, check_pending)[0]
+
+    def _index_address_rows_many(self, addresses: Sequence[str], stake_sel: int,
+                                 check_pending: bool) -> List[List[Tuple[str, int, int]]]:
+        """:meth:`_index_address_rows` of each address, in the order given: every byte form of every address
+        goes into one ``address_outputs_many`` call, which a GPU node answers with one pass over the HBM
+        table (the reference's ``address = ANY($1)`` takes the list natively)."""
+        forms = [[bytes.fromhex(h) for h in codec.address_search_hex(a)] for a in addresses]
         pend = (self.gov.pending_spent(True) if self.gov is not None else self._pending_spent_set()) \
             if check_pending else set()
-        out = []
-        for h in codec.address_search_hex(address):
-            recs, pay, _ = self.utxo.address_outputs(bytes.fromhex(h), (TAG_BY_TABLE['unspent_outputs'],), stake_sel)
-            idx = recs[:, 32:36].copy().view('<u4').ravel()
-            for k in range(len(recs)):
-                key = (bytes(recs[k, :32]).hex(), int(idx[k]))
-                if key not in pend:
-                    out.append((key[0], key[1], int(pay['amount'][k])))
-        out.sort(key=lambda r: (r[0], r[1]))
-        return out
+        tags = (TAG_BY_TABLE['unspent_outputs'],)
+        res = iter(self.utxo.address_outputs_many([(f, tags, stake_sel) for fs in forms for f in fs]))
+        rows = []
+        for fs in forms:
+            out = []
+            for _ in fs:
+                recs, pay, _total = next(res)
+                idx = recs[:, 32:36].copy().view('<u4').ravel()
+                for k in range(len(recs)):
+                    key = (bytes(recs[k, :32]).hex(), int(idx[k]))
+                    if key not in pend:
+                        out.append((key[0], key[1], int(pay['amount'][k])))
+            out.sort(key=lambda r: (r[0], r[1]))
+            rows.append(out)
+        return rows
 
     async def get_spendable_outputs(self, address: str, check_pending_txs: bool = False) -> List[TransactionInput]:
         point = string_to_point(address)
@@ -2920,6 +2933,18 @@ class Database:
                                  'AND (unspent_outputs.is_stake IS NULL OR unspent_outputs.is_stake = 0)',
                                  check_pending_txs)
         return [TransactionInput(h, i, amount=Decimal(a) / SMALLEST, public_key=point) for h, i, a in rows]
+
+    async def get_spendable_outputs_many(self, addresses: Sequence[str],
+                                         check_pending_txs: bool = False) -> Dict[str, List[TransactionInput]]:
+        """``get_spendable_outputs`` of every address, from one pass over the UTXO index."""
+        addresses = list(dict.fromkeys(addresses))
+        if not self.address_queries_from_index:
+            return {a: await self.get_spendable_outputs(a, check_pending_txs) for a in addresses}
+        from .utxo import STAKE_EXCLUDE
+        points = [string_to_point(a) for a in addresses]
+        rows = self._index_address_rows_many(addresses, STAKE_EXCLUDE, check_pending_txs)
+        return {a: [TransactionInput(h, i, amount=Decimal(am) / SMALLEST, public_key=p) for h, i, am in r]
+                for a, p, r in zip(addresses, points, rows)}
 
     async def get_stake_outputs(self, address: str, check_pending_txs: bool = False) -> List[TransactionInput]:
         point = string_to_point(address)
@@ -3066,19 +3091,46 @@ class Database:
         return round_up_decimal(sum(ratio, Decimal(0)))
 
     async def get_address_balance(self, address: str, check_pending_txs: bool = False) -> Decimal:
-        forms = self._forms(address)
         balance = sum([i.amount for i in await self.get_spendable_outputs(address, check_pending_txs)], Decimal(0))
         if check_pending_txs:
-            search = self._search(address)
-            for r in self._q('SELECT tx_hex FROM pending_transactions ORDER BY rowid'):
-                if not any(s in r['tx_hex'] for s in search):
-                    continue
-                tx = await Transaction.from_hex(r['tx_hex'], check_signatures=False)
-                for o in tx.outputs:
-                    if o.address in forms and o.transaction_type is OutputType.REGULAR and \
-                            (o.is_stake is False or o.is_stake is None):
-                        balance += o.amount
+            balance += await self._pending_regular_income(address, self._pending_hexes())
         return balance
+
+    def _pending_hexes(self) -> List[list]:
+        """[tx_hex, parsed transaction or None] of every pending transaction, in arrival order."""
+        return [[r['tx_hex'], None] for r in self._q('SELECT tx_hex FROM pending_transactions ORDER BY rowid')]
+
+    async def _pending_regular_income(self, address: str, pending: List[list]) -> Decimal:
+        """Regular, non-stake amounts that the ``pending`` transactions (:meth:`_pending_hexes`) pay to
+        ``address``; a transaction is parsed once, when the first address's search pattern hits its hex."""
+        forms, search = self._forms(address), self._search(address)
+        income = Decimal(0)
+        for p in pending:
+            if not any(s in p[0] for s in search):
+                continue
+            if p[1] is None:
+                p[1] = await Transaction.from_hex(p[0], check_signatures=False)
+            for o in p[1].outputs:
+                if o.address in forms and o.transaction_type is OutputType.REGULAR and \
+                        (o.is_stake is False or o.is_stake is None):
+                    income += o.amount
+        return income
+
+    async def get_address_balances(self, addresses: Sequence[str],
+                                   check_pending_txs: bool = False) -> Dict[str, Decimal]:
+        """``get_address_balance`` of every address, from one pass over the UTXO index (and one read of the
+        pending transactions)."""
+        addresses = list(dict.fromkeys(addresses))
+        if not self.address_queries_from_index:
+            return {a: await self.get_address_balance(a, check_pending_txs) for a in addresses}
+        outs = await self.get_spendable_outputs_many(addresses, check_pending_txs)
+        pending = self._pending_hexes() if check_pending_txs else []
+        out = {}
+        for a in addresses:
+            out[a] = sum([i.amount for i in outs[a]], Decimal(0))
+            if check_pending_txs:
+                out[a] += await self._pending_regular_income(a, pending)
+        return out
 
     async def get_pending_stake_transaction(self, address: str):
         search = self._search(address)

@@ -152,6 +152,10 @@ class _HostBackend:
         pay = np.frombuffer(b''.join(self.p[k] for k in hits), dtype=PAYLOAD_DTYPE)
         return pack_records(hits, [self.d[k] for k in hits]), pay
 
+    def address_scan_batch(self, queries):
+        """``address_scan`` for each (addr, tag_mask, stake_sel): the owner map answers each directly."""
+        return [self.address_scan(a, m, s) for a, m, s in queries]
+
     @staticmethod
     def _addr(raw: Optional[bytes]) -> bytes:
         if not raw:
@@ -230,6 +234,10 @@ class _NativeHostBackend:
     def address_scan(self, addr: bytes, tag_mask: int, stake_sel: int = STAKE_ANY):
         raw, pay = self.t.address_scan(bytes(addr), tag_mask, stake_sel)
         return raw.reshape(-1, 40), pay.view(PAYLOAD_DTYPE)
+
+    def address_scan_batch(self, queries):
+        """``address_scan`` for each (addr, tag_mask, stake_sel): the owner map answers each directly."""
+        return [self.address_scan(a, m, s) for a, m, s in queries]
 
     def __len__(self):
         return len(self.t)
@@ -354,6 +362,28 @@ class _GpuBackend:
     def address_scan(self, addr: bytes, tag_mask: int, stake_sel: int = STAKE_ANY):
         raw, pay, _total = self.L.utxo_address_scan(self.h, addr, tag_mask, stake_sel)
         return np.frombuffer(raw, dtype=np.uint8).reshape(-1, 40), np.frombuffer(pay, dtype=PAYLOAD_DTYPE)
+
+    def address_scan_batch(self, queries):
+        """``address_scan`` for each (addr, tag_mask, stake_sel), all answered by ONE pass over the HBM table
+        (``utxo_address_scan_batch``: the queries are a device-resident table sorted by fingerprint)."""
+        n = len(queries)
+        if not n:
+            return []
+        addrs = np.zeros((n, 64), dtype=np.uint8)
+        lens = np.zeros(n, dtype=np.uint32)
+        for k, (a, _, _) in enumerate(queries):
+            if len(a) > 64:
+                raise ValueError('address is at most 64 bytes')
+            addrs[k, :len(a)] = np.frombuffer(bytes(a), dtype=np.uint8)
+            lens[k] = len(a)
+        masks = np.array([m for _, m, _ in queries], dtype=np.uint32)
+        sels = np.array([s for _, _, s in queries], dtype=np.uint32)
+        qidx, raw, pay, _totals = self.L.utxo_address_scan_batch(self.h, addrs, lens, masks, sels)
+        recs = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 40)
+        pay = np.frombuffer(pay, dtype=PAYLOAD_DTYPE)
+        order = np.argsort(qidx, kind='stable')
+        cuts = np.searchsorted(qidx[order], np.arange(n + 1))
+        return [(recs[order[cuts[k]:cuts[k + 1]]], pay[order[cuts[k]:cuts[k + 1]]]) for k in range(n)]
 
     def records_payload(self):
         raw, pay = self.L.utxo_dump_payload(self.h)
@@ -575,6 +605,25 @@ class UtxoIndex:
         order = sort_order(np.ascontiguousarray(recs))
         recs, pay = np.ascontiguousarray(recs[order]), np.ascontiguousarray(pay[order])
         return recs, pay, int(pay['amount'].sum()) if len(pay) else 0
+
+    @_locked
+    def address_outputs_many(self, queries: Sequence[Tuple[bytes, Iterable[int], int]]):
+        """:meth:`address_outputs` for each ``(addr, tags, stake_sel)`` of ``queries``: one
+        ``(records, payloads, amount_sum)`` per query, in query order, each what the single call returns.
+        GPU backend: every query is answered by the same pass over the HBM table
+        (``utxo_address_scan_batch``), where single calls make one pass each."""
+        qs = []
+        for addr, tags, stake_sel in queries:
+            mask = 0
+            for t in tags:
+                mask |= 1 << int(t)
+            qs.append((bytes(addr), mask, int(stake_sel)))
+        out = []
+        for recs, pay in self.be.address_scan_batch(qs):
+            order = sort_order(np.ascontiguousarray(recs))
+            recs, pay = np.ascontiguousarray(recs[order]), np.ascontiguousarray(pay[order])
+            out.append((recs, pay, int(pay['amount'].sum()) if len(pay) else 0))
+        return out
 
     @_locked
     def records_payload(self, sort: bool = True):

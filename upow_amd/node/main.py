@@ -951,6 +951,20 @@ async def get_address_info(request: Request, address: str, show_pending: bool = 
     }}
 
 
+@app.post('/get_addresses_info')
+@limiter.limit('15/second')
+async def get_addresses_info(request: Request,
+                             addresses: Annotated[list[str], Body(min_length=1, max_length=1000)],
+                             check_pending_txs: Annotated[bool, Body()] = False):
+    """Balance and spendable outputs of up to 1000 addresses (the project's own route; the reference answers
+    one address per request): body ``{"addresses": [...], "check_pending_txs": false}``, one entry per
+    requested address in request order, each formatted like ``/get_address_info``. The UTXO index answers
+    the whole list from one pass (K14, ``utxo_address_scan_batch`` on a GPU node)."""
+    outputs = await db.get_spendable_outputs_many(addresses, check_pending_txs)
+    return {'ok': True, 'result': [{'address': a, 'balance': '{:f}'.format(sum(o.amount for o in outputs[a])),
+                                    'spendable_outputs': _outs(outputs[a])} for a in addresses]}
+
+
 @app.get('/get_address_transactions')
 async def get_address_transactions(request: Request, address: str, page: int = Query(default=1, ge=1),
                                    limit: int = Query(default=5, le=1000)):

@@ -92,11 +92,15 @@ async def main(argv=None):
         return
     if cmd == 'balance':
         total = total_pending = 0
-        for kp in store.get('keys') or []:
-            address = point_to_string(op.public_key(int(kp['private_key'])))
-            bal = await database.get_address_balance(address)
+        keys = store.get('keys') or []
+        addresses = [point_to_string(op.public_key(int(kp['private_key']))) for kp in keys]
+        # every key's balance from one pass over the UTXO index each, not two passes per key
+        balances = await database.get_address_balances(addresses)
+        pending_balances = await database.get_address_balances(addresses, True)
+        for kp, address in zip(keys, addresses):
+            bal = balances[address]
             stake = await database.get_address_stake(address)
-            pbal = await database.get_address_balance(address, True)
+            pbal = pending_balances[address]
             pstake = await database.get_address_stake(address, True)
             total += bal
             total_pending += pbal
