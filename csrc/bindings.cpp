@@ -145,6 +145,11 @@ PYBIND11_MODULE(_native, m) {
     m.def("pow_check_word", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
                                uint32_t v) { return pow_check_word_host(make_job(header, tmask, tword, fs, fl), v); });
 
+    m.def("pow_variant_count", []() { return pow_variant_count(); });
+    m.def("pow_job_h0", [](py::bytes header, uint32_t v) { return pow_job_h0_host(make_job(header, 0, 0, 0, 16), v); },
+          py::arg("header"), py::arg("v"),
+          "digest word H0 for nonce word v, from the precomputed job constants of the GPU kernel (host arithmetic)");
+
     m.def("pow_search_host", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
                                 uint64_t start, uint64_t count, int threads) {
         PowJobHost j = make_job(header, tmask, tword, fs, fl);

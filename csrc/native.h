@@ -24,6 +24,9 @@ struct PowKernelInfo {
     int cus = 0, blocks_per_cu = 0, resident_blocks = 0;
 };
 PowKernelInfo pow_kernel_info(int variant);
+int pow_variant_count();  // kernel variants are numbered 0 (the default) .. pow_variant_count() - 1
+// H0 of SHA256(header with nonce word v) computed on the host from the job constants the GPU kernel uses
+uint32_t pow_job_h0_host(const PowJobHost& job, uint32_t v);
 
 bool pow_check_word_host(const PowJobHost& job, uint32_t v);
 PowResult pow_search_host(const PowJobHost& job, uint64_t start, uint64_t count, int threads);

@@ -9,15 +9,17 @@
 //  * v2 header (108 B): the tail block's words W0..W9 are nonce independent too, so the host also
 //    runs rounds 0..9 and the kernel starts at round 10 (W10 = the nonce word);
 //    v1 header (138 B): the nonce straddles W1/W2 of the third block; the kernel starts at round 1;
-//  * every job constant is a kernel argument -> SGPRs; all loop-invariant partial sums of the message
-//    schedule are hoisted by the compiler (LICM + reassociation) so the loop body only contains the
-//    nonce-dependent work;
+//  * every job constant is a kernel argument -> SGPRs, and so is every nonce-independent value of the
+//    tail block (constant schedule words folded with K, the constant part of partly constant words, the
+//    first dependent round's sums): make_pow_job computes them once per job, so no lane-uniform value is
+//    computed with VALU rotates in the prologue and kept in a VGPR for the loop (61 VGPRs, 8 waves/SIMD;
+//    the compiler-hoisted form of the same loop, kept as variant 3, needs 85 VGPRs -> 5 waves/SIMD);
 //  * the message schedule is kept in VGPRs (a 16-entry rolling window), not LDS: each W word is
 //    produced once and consumed 4x within ~16 rounds; an LDS round trip per use would add a
 //    ds_write+4 ds_read per word (≈240 LDS dword ops per nonce) against ≈1.2k VALU ops, making LDS a
 //    co-bottleneck (MI355X_MICROARCH.md §LDS: 32 dwords/clk/CU for b32 vs 128 VALU lane-ops/clk/CU);
 //  * rotates lower to v_alignbit_b32, the 3-input XORs of the Sigma functions and Maj to the gfx950
-//    v_bitop3_b32 (truth tables 0x96 / 0xE8), 3-input adds to v_add3_u32 (1110 VALU ops per nonce in
+//    v_bitop3_b32 (truth tables 0x96 / 0xE8), 3-input adds to v_add3_u32 (1107 VALU ops per nonce in
 //    the v2 loop body vs 1359 with 2-input XORs);
 //  * the predicate only needs digest word H0 for difficulty < 8 (8 hex nibbles) -> one compare per
 //    nonce; hits are appended with an atomic to a small candidate list and re-checked exactly on the
@@ -43,7 +45,33 @@ struct PowJobDev {
     uint32_t tword;
     uint32_t frac_shift;  // right shift of H0 that brings the fractional nibble to bits 0..3
     uint32_t frac_limit;  // nibble must be < frac_limit (16 == no fractional check)
+    // Nonce-independent values of the tail block, computed once per job on the host (make_pow_job) and read
+    // by pow_h0_pre as kernel arguments, i.e. from SGPRs. R0 = first nonce-dependent round (v2: 10, v1: 1).
+    uint32_t ca, ce;   // round R0 with a constant state: a' = ca + W[R0], e' = ce + W[R0]
+    uint32_t hk[3];    // rounds R0+1..R0+3, whose h is still constant: h + K[i] (+ W[i] where W[i] is constant)
+    uint32_t kw[64];   // W[i] constant: K[i] + W[i]; W[i] partly constant (i >= 16): the sum of its constant terms
 };
+
+// Which words of the tail block's message schedule depend on the nonce (vec) and, of those, which also have
+// nonce-independent terms (has_const). Shared by the host precomputation and the unrolled device loop.
+struct PowWordKinds {
+    bool vec[64];
+    bool has_const[64];
+};
+constexpr PowWordKinds pow_word_kinds(int layout) {
+    PowWordKinds k{};
+    for (int i = 0; i < 16; ++i) k.vec[i] = layout == 2 ? i == 10 : (i == 1 || i == 2);
+    for (int i = 16; i < 64; ++i) {
+        const int src[4] = {i - 16, i - 15, i - 7, i - 2};
+        bool v = false, c = false;
+        for (int t = 0; t < 4; ++t) {
+            if (k.vec[src[t]]) v = true; else c = true;
+        }
+        k.vec[i] = v;
+        k.has_const[i] = v && c;
+    }
+    return k;
+}
 
 #define ROTR(x, n) __builtin_amdgcn_alignbit((x), (x), (n))
 // gfx950 v_bitop3_b32: 3-input bitwise op from an 8-bit truth table. XOR3 (0x96) and MAJ (0xE8) are
@@ -94,6 +122,61 @@ __device__ __forceinline__ uint32_t pow_h0(const PowJobDev& job, uint32_t v) {
         }
         uint32_t t1 = h + BSIG1(e) + CH(e, f, g) + dK[i] + wi;
         uint32_t t2 = BSIG0(a) + MAJ(a, b, c);
+        h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
+    }
+    return job.mid[0] + a;
+}
+
+// The same H0 from the host-precomputed constants of PowJobDev: no lane-uniform value is computed (or kept in
+// a VGPR) on the device, and K comes from the compile-time table. Compiled for the host too, where the
+// tests check the precomputed constants against hashlib (pow_job_h0_host).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define P_ROTR(x, n) ROTR(x, n)
+#define P_XOR3(a, b, c) XOR3(a, b, c)
+#define P_MAJ(a, b, c) MAJ(a, b, c)
+#else
+#define P_ROTR(x, n) host_rotr((x), (n))
+#define P_XOR3(a, b, c) ((a) ^ (b) ^ (c))
+#define P_MAJ(a, b, c) (((a) & (b)) ^ ((a) & (c)) ^ ((b) & (c)))
+#endif
+#define P_BSIG0(x) P_XOR3(P_ROTR((x), 2), P_ROTR((x), 13), P_ROTR((x), 22))
+#define P_BSIG1(x) P_XOR3(P_ROTR((x), 6), P_ROTR((x), 11), P_ROTR((x), 25))
+#define P_SSIG0(x) P_XOR3(P_ROTR((x), 7), P_ROTR((x), 18), ((x) >> 3))
+#define P_SSIG1(x) P_XOR3(P_ROTR((x), 17), P_ROTR((x), 19), ((x) >> 10))
+
+template <int LAYOUT>
+__host__ __device__ __forceinline__ uint32_t pow_h0_pre(const PowJobDev& job, uint32_t v) {
+    constexpr int R0 = LAYOUT == 2 ? 10 : 1;
+    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
+    uint32_t w[16] = {};  // only the nonce-dependent words ever live here
+    if (LAYOUT == 2) {
+        w[10] = v;
+    } else {
+        w[1] = job.w[1] | ((v & 0xffu) << 8) | ((v >> 8) & 0xffu);
+        w[2] = job.w[2] | (((v >> 16) & 0xffu) << 24) | ((v >> 24) << 16);
+    }
+    uint32_t a = job.ca + w[R0], b = job.st[0], c = job.st[1], d = job.st[2];
+    uint32_t e = job.ce + w[R0], f = job.st[4], g = job.st[5], h = 0;
+#pragma unroll
+    for (int i = R0 + 1; i < 64; ++i) {
+        uint32_t wi = 0;
+        if (kinds.vec[i]) {
+            if (i < 16) {
+                wi = w[i];
+            } else {
+                if (kinds.has_const[i]) wi = job.kw[i];
+                if (kinds.vec[i - 16]) wi += w[i & 15];
+                if (kinds.vec[i - 15]) wi += P_SSIG0(w[(i - 15) & 15]);
+                if (kinds.vec[i - 7]) wi += w[(i - 7) & 15];
+                if (kinds.vec[i - 2]) wi += P_SSIG1(w[(i - 2) & 15]);
+                w[i & 15] = wi;
+            }
+        }
+        uint32_t x;  // h + K[i] + W[i]
+        if (i <= R0 + 3) x = kinds.vec[i] ? job.hk[i - R0 - 1] + wi : job.hk[i - R0 - 1];
+        else x = kinds.vec[i] ? h + kSha256K[i] + wi : h + job.kw[i];
+        const uint32_t t1 = x + P_BSIG1(e) + CH(e, f, g);
+        const uint32_t t2 = P_BSIG0(a) + P_MAJ(a, b, c);
         h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
     }
     return job.mid[0] + a;
@@ -160,6 +243,22 @@ __global__ __launch_bounds__(256, MIN_WAVES_PER_SIMD) void pow_search_kernel(Pow
     }
 }
 
+template <int LAYOUT, int MIN_WAVES_PER_SIMD>
+__global__ __launch_bounds__(256, MIN_WAVES_PER_SIMD) void pow_search_pre_kernel(PowJobDev job, uint32_t v_base, uint32_t iters,
+                                                             uint32_t* __restrict__ out_count,
+                                                             uint32_t* __restrict__ out_words, uint32_t cap) {
+    const uint32_t nthreads = gridDim.x * blockDim.x;
+    uint32_t v = v_base + blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint32_t it = 0; it < iters; ++it, v += nthreads) {
+        const uint32_t h0 = pow_h0_pre<LAYOUT>(job, v);
+        const bool hit = ((h0 ^ job.tword) & job.tmask) == 0 && ((h0 >> job.frac_shift) & 0xfu) < job.frac_limit;
+        if (__builtin_expect(hit, 0)) {
+            const uint32_t slot = atomicAdd(out_count, 1u);
+            if (slot < cap) out_words[slot] = v;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -194,7 +293,47 @@ PowJobDev make_pow_job(const PowJobHost& hj) {
     j.tword = hj.tword;
     j.frac_shift = hj.frac_shift;
     j.frac_limit = hj.frac_limit;
+    // nonce-independent values for pow_h0_pre
+    const int r0 = len == 108 ? 10 : 1;
+    const PowWordKinds kinds = pow_word_kinds(len == 108 ? 2 : 1);
+    auto ssig0 = [](uint32_t x) { return host_rotr(x, 7) ^ host_rotr(x, 18) ^ (x >> 3); };
+    auto ssig1 = [](uint32_t x) { return host_rotr(x, 17) ^ host_rotr(x, 19) ^ (x >> 10); };
+    uint32_t wc[64] = {0};  // the constant words' values
+    for (int i = 0; i < 64; ++i) {
+        if (i < 16) {
+            if (!kinds.vec[i]) wc[i] = j.w[i];
+        } else {
+            uint32_t sum = 0;
+            if (!kinds.vec[i - 16]) sum += wc[i - 16];
+            if (!kinds.vec[i - 15]) sum += ssig0(wc[i - 15]);
+            if (!kinds.vec[i - 7]) sum += wc[i - 7];
+            if (!kinds.vec[i - 2]) sum += ssig1(wc[i - 2]);
+            if (!kinds.vec[i]) wc[i] = sum;
+            else j.kw[i] = sum;
+        }
+        if (!kinds.vec[i]) j.kw[i] = kSha256K[i] + wc[i];
+    }
+    {
+        const uint32_t* s = j.st;
+        const uint32_t t1 = s[7] + (host_rotr(s[4], 6) ^ host_rotr(s[4], 11) ^ host_rotr(s[4], 25)) +
+                            ((s[4] & s[5]) ^ (~s[4] & s[6])) + kSha256K[r0];
+        const uint32_t t2 = (host_rotr(s[0], 2) ^ host_rotr(s[0], 13) ^ host_rotr(s[0], 22)) +
+                            ((s[0] & s[1]) ^ (s[0] & s[2]) ^ (s[1] & s[2]));
+        j.ce = s[3] + t1;
+        j.ca = t1 + t2;
+        for (int k = 0; k < 3; ++k) {
+            const int i = r0 + 1 + k;
+            j.hk[k] = s[6 - k] + (kinds.vec[i] ? kSha256K[i] : j.kw[i]);
+        }
+    }
     return j;
+}
+
+// H0 of SHA256(header with nonce word v) through pow_h0_pre on the host: the kernel's arithmetic on the
+// precomputed job constants, for the tests.
+uint32_t pow_job_h0_host(const PowJobHost& hj, uint32_t v) {
+    const PowJobDev job = make_pow_job(hj);
+    return hj.header.size() == 108 ? pow_h0_pre<2>(job, v) : pow_h0_pre<1>(job, v);
 }
 
 struct PowDeviceBuffers {
@@ -220,23 +359,43 @@ static PowDeviceBuffers& pow_buffers(uint32_t cap) {
     return b;
 }
 
+// Kernel variants (bench.py --variant / UPOW_POW_VARIANT, scripts/pow_variants.py A/Bs them in one process):
+//  1  the original loop forced to 8 waves/SIMD (spills)          2  message schedule staged in LDS
+//  3  the original loop: K from a __constant__ table, uniforms hoisted by the compiler into VGPRs
+//  4  host-precomputed uniforms in SGPRs (pow_h0_pre): 62 VGPRs, 103 SGPRs -> 7 waves/SIMD
+//  5  as 4 with the SGPR budget of 8 waves/SIMD: the compiler re-materialises K words with s_mov in the loop
+//     (SALU, no extra VALU), 61 VGPRs, no scratch
+//  0  the default, kPowDefaultVariant
+// v1 headers have the original loop (1-3) and the precomputed one (4, 5) only.
+constexpr int kPowDefaultVariant = 5;
+constexpr int kPowVariantCount = 6;
+
+using PowKernelFn = void (*)(PowJobDev, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t);
+
+static PowKernelFn pow_kernel_fn(bool v2, int variant) {
+    if (variant < 0 || variant >= kPowVariantCount) throw std::invalid_argument("unknown PoW kernel variant");
+    if (variant == 0) variant = kPowDefaultVariant;
+    // v1 at 7 waves/SIMD: left to itself the compiler takes 106 SGPRs and spills some to VGPR lanes in the loop
+    if (!v2) return variant >= 4 ? &pow_search_pre_kernel<1, 7> : &pow_search_kernel<1, 1>;
+    switch (variant) {
+        case 1: return &pow_search_kernel<2, 8>;
+        case 2: return &pow_search_lds_kernel;
+        case 4: return &pow_search_pre_kernel<2, 1>;
+        case 5: return &pow_search_pre_kernel<2, 8>;
+        default: return &pow_search_kernel<2, 1>;
+    }
+}
+
+int pow_variant_count() { return kPowVariantCount; }
+
 // Grid = exactly the resident capacity of the chip (CUs x blocks/CU for this kernel's VGPR/SGPR use),
-// so every launch is one full "wave" of workgroups with no tail round. The occupancy API can report
-// one block/CU too many for SGPR-heavy kernels (MI355X_MICROARCH.md §Residency), which would only
-// create a small second round here, so we take min(API, 800 / (ceil(sgpr/16)*16 + 16)).
+// so every launch is one full "wave" of workgroups with no tail round.
 static int pow_resident_blocks(bool v2, int variant) {
     int dev = 0, cus = 0, per_cu = 0;
     hip_check(hipGetDevice(&dev), "hipGetDevice");
     hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "attr");
-    const void* fn = v2 ? (variant == 1   ? reinterpret_cast<const void*>(&pow_search_kernel<2, 8>)
-                           : variant == 2 ? reinterpret_cast<const void*>(&pow_search_lds_kernel)
-                                          : reinterpret_cast<const void*>(&pow_search_kernel<2, 1>))
-                        : reinterpret_cast<const void*>(&pow_search_kernel<1, 1>);
+    const void* fn = reinterpret_cast<const void*>(pow_kernel_fn(v2, variant));
     hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0), "occupancy");
-    hipFuncAttributes attr{};
-    if (hipFuncGetAttributes(&attr, fn) == hipSuccess) {
-        (void)attr;
-    }
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
     return cus * per_cu;
@@ -258,6 +417,7 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
                          uint32_t chunk_iters, uint32_t cap, int variant) {
     PowJobDev job = make_pow_job(hj);
     const bool v2 = hj.header.size() == 108;
+    const PowKernelFn kernel = pow_kernel_fn(v2, variant);
     node_device_enter();  // a rank's search from any of its threads runs on the rank's own GPU
     PowDeviceBuffers& buf = pow_buffers(cap);
     hipStream_t st = miner_stream();  // least priority: node kernels go first (csrc/streams.h)
@@ -291,18 +451,7 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
             }
         }
         const uint32_t vb = uint32_t(start + done);
-        if (v2 && variant == 2)
-            hipLaunchKernelGGL(pow_search_lds_kernel, dim3(gb), dim3(block), 0, st, job, vb, iters, buf.d_count,
-                               buf.d_words, cap);
-        else if (v2 && variant == 1)
-            hipLaunchKernelGGL((pow_search_kernel<2, 8>), dim3(gb), dim3(block), 0, st, job, vb, iters,
-                               buf.d_count, buf.d_words, cap);
-        else if (v2)
-            hipLaunchKernelGGL((pow_search_kernel<2, 1>), dim3(gb), dim3(block), 0, st, job, vb, iters,
-                               buf.d_count, buf.d_words, cap);
-        else
-            hipLaunchKernelGGL((pow_search_kernel<1, 1>), dim3(gb), dim3(block), 0, st, job, vb, iters,
-                               buf.d_count, buf.d_words, cap);
+        hipLaunchKernelGGL(kernel, dim3(gb), dim3(block), 0, st, job, vb, iters, buf.d_count, buf.d_words, cap);
         hip_check(hipGetLastError(), "pow_search_kernel launch");
         done += uint64_t(iters) * gb * block;
     }
