@@ -150,6 +150,11 @@ PYBIND11_MODULE(_native, m) {
           py::arg("header"), py::arg("v"),
           "digest word H0 for nonce word v, from the precomputed job constants of the GPU kernel (host arithmetic)");
 
+    m.def("pow_job_h0_variant", [](py::bytes header, uint32_t v, int variant) {
+              return pow_job_h0_host(make_job(header, 0, 0, 0, 16), v, variant); },
+          py::arg("header"), py::arg("v"), py::arg("variant"),
+          "pow_job_h0 through the device function of one kernel variant (host arithmetic)");
+
     m.def("pow_search_host", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
                                 uint64_t start, uint64_t count, int threads) {
         PowJobHost j = make_job(header, tmask, tword, fs, fl);

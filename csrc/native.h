@@ -27,6 +27,7 @@ PowKernelInfo pow_kernel_info(int variant);
 int pow_variant_count();  // kernel variants are numbered 0 (the default) .. pow_variant_count() - 1
 // H0 of SHA256(header with nonce word v) computed on the host from the job constants the GPU kernel uses
 uint32_t pow_job_h0_host(const PowJobHost& job, uint32_t v);
+uint32_t pow_job_h0_host(const PowJobHost& job, uint32_t v, int variant);  // through variant's device function
 
 bool pow_check_word_host(const PowJobHost& job, uint32_t v);
 PowResult pow_search_host(const PowJobHost& job, uint64_t start, uint64_t count, int threads);

@@ -21,6 +21,9 @@
 //  * rotates lower to v_alignbit_b32, the 3-input XORs of the Sigma functions and Maj to the gfx950
 //    v_bitop3_b32 (truth tables 0x96 / 0xE8), 3-input adds to v_add3_u32 (1107 VALU ops per nonce in
 //    the v2 loop body vs 1359 with 2-input XORs);
+//  * the default v2 kernel (pow_h0_sched, variant 9) issues pow_h0_pre's instructions in a pinned order with an
+//    s_sleep 0 in front of every v_alignbit_b32 and v_add3_u32: behind that sequencer-only instruction the two
+//    slow opcodes cost about a cycle less (3.66 against 3.94 cycles per VALU instruction, docs/PERF.md);
 //  * the predicate only needs digest word H0 for difficulty < 8 (8 hex nibbles) -> one compare per
 //    nonce; hits are appended with an atomic to a small candidate list and re-checked exactly on the
 //    host (covers d >= 8 and the d < 1 "whole hash" quirk).
@@ -30,6 +33,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 #include "native.h"
 #include "streams.h"
@@ -139,6 +143,12 @@ __device__ __forceinline__ uint32_t pow_h0(const PowJobDev& job, uint32_t v) {
 #define P_XOR3(a, b, c) ((a) ^ (b) ^ (c))
 #define P_MAJ(a, b, c) (((a) & (b)) ^ ((a) & (c)) ^ ((b) & (c)))
 #endif
+// Ch(e, f, g) as one v_bitop3_b32 whatever the operands (a second uniform operand costs a v_mov before the loop)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define P_CH(e, f, g) __builtin_amdgcn_bitop3_b32((e), (f), (g), 0xCA)
+#else
+#define P_CH(e, f, g) CH(e, f, g)
+#endif
 #define P_BSIG0(x) P_XOR3(P_ROTR((x), 2), P_ROTR((x), 13), P_ROTR((x), 22))
 #define P_BSIG1(x) P_XOR3(P_ROTR((x), 6), P_ROTR((x), 11), P_ROTR((x), 25))
 #define P_SSIG0(x) P_XOR3(P_ROTR((x), 7), P_ROTR((x), 18), ((x) >> 3))
@@ -180,6 +190,290 @@ __host__ __device__ __forceinline__ uint32_t pow_h0_pre(const PowJobDev& job, ui
         h = g; g = f; f = e; e = d + t1; d = c; c = b; b = a; a = t1 + t2;
     }
     return job.mid[0] + a;
+}
+
+// pow_h0_pre<2> with the order of its instructions written out and pinned (variants 6..9): the same
+// arithmetic on the same PowJobDev constants, instruction for instruction, so only the issue order differs.
+//  D         schedule run-ahead: word W[i+D] is produced during round i, one of its (up to ten) instructions
+//            after each of the round's first ten; D = 0 produces W[i] in one piece just before round i.
+//  TWO_PATH  within a round the Sigma1/Ch/t1 path alternates with the Sigma0/Maj path and h + K + W, so that no
+//            instruction follows its producer directly; otherwise the round runs path after path.
+//  FILL      an s_sleep 0 in front of 1: every rotate, 2: every rotate and add3 (the two opcodes that issue at
+//            4.1 cycles). It sleeps for no time and is handled by the sequencer, not the VALU; with it in front
+//            the slow instruction costs about one cycle less (docs/PERF.md, "PoW issue order").
+// The order is held by empty asm statements that emit nothing. The one after instruction n reads n's result,
+// so n comes before it, and redefines ("+v") a VGPR input of instruction n+2, so n+2 comes after it; volatile
+// asm statements keep their own order, and a sched_barrier after each keeps the machine scheduler from
+// moving n+1 in front of it. (Redefining an input of n+1 itself is no option: the hazard pass puts an s_nop
+// between an asm statement's VGPR result and an instruction that reads it at once.)
+// Rounds R0+1..R0+3, whose state is still partly uniform, and the words that are due before the first pinned
+// round produces them are left to the compiler.
+struct PowSchedRegs {
+    uint32_t w[16];  // the rolling window; only nonce-dependent words ever live here
+    uint32_t s[8];   // a..h, rotating: in round i, a = s[-i & 7] .. h = s[(7 - i) & 7]
+    uint32_t t[4], u[4], q[3];  // temporaries of the schedule word, the Sigma1/Ch path and the Sigma0/Maj path
+};
+// What one instruction is pinned by: its VGPR inputs and its result (all null: the instruction does not exist)
+struct PowOpRegs {
+    uint32_t* in[3] = {nullptr, nullptr, nullptr};
+    uint32_t* out = nullptr;
+    __host__ __device__ __forceinline__ bool reads(const uint32_t* p) const {
+        return p != nullptr && (in[0] == p || in[1] == p || in[2] == p);
+    }
+};
+
+// Instruction k (0..9) of schedule word W[j]; instructions of terms that are nonce independent do not exist.
+//  0-3 sigma0(W[j-15]) -> t[0]    4-7 sigma1(W[j-2]) -> t[1]    8 the first add of a four-term sum    9 W[j]
+constexpr bool pow_sched_op_exists(const PowWordKinds& kinds, int j, int k) {
+    if (j < 16 || j > 63 || !kinds.vec[j]) return false;
+    if (k < 4) return kinds.vec[j - 15];
+    if (k < 8) return kinds.vec[j - 2];
+    const int n = int(kinds.has_const[j]) + int(kinds.vec[j - 16]) + int(kinds.vec[j - 15]) + int(kinds.vec[j - 7]) +
+                  int(kinds.vec[j - 2]);
+    return k == 9 || n == 4;
+}
+
+// RUN: execute the instruction; otherwise only name its registers
+template <int LAYOUT, int J, int K, bool RUN>
+__host__ __device__ __forceinline__ PowOpRegs pow_sched_op(const PowJobDev& job, PowSchedRegs& r) {
+    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
+    PowOpRegs o;
+    if constexpr (pow_sched_op_exists(kinds, J, K)) {
+        constexpr int j = J, k = K;
+        constexpr bool c = kinds.has_const[j], v16 = kinds.vec[j - 16], v15 = kinds.vec[j - 15],
+                       v7 = kinds.vec[j - 7], v2 = kinds.vec[j - 2];
+        uint32_t(&w)[16] = r.w;
+        uint32_t(&t)[4] = r.t;
+        uint32_t& x15 = w[(j - 15) & 15];
+        uint32_t& x2 = w[(j - 2) & 15];
+        if constexpr (k < 4) {
+            if (k == 3) o = {{&t[2], &t[1], &t[0]}, &t[0]};
+            else o = {{&x15, nullptr, nullptr}, &t[k]};
+            if (RUN) *o.out = k == 0 ? P_ROTR(x15, 7) : k == 1 ? P_ROTR(x15, 18) : k == 2 ? x15 >> 3 : P_XOR3(t[0], t[1], t[2]);
+        } else if constexpr (k < 8) {
+            if (k == 7) o = {{&t[3], &t[2], &t[1]}, &t[1]};
+            else o = {{&x2, nullptr, nullptr}, &t[k - 3]};
+            if (RUN) *o.out = k == 4 ? P_ROTR(x2, 17) : k == 5 ? P_ROTR(x2, 19) : k == 6 ? x2 >> 10 : P_XOR3(t[1], t[2], t[3]);
+        } else {
+            constexpr int n = int(c) + int(v16) + int(v15) + int(v7) + int(v2);
+            uint32_t* reg[7] = {};  // the sum's terms that are in VGPRs, in the order they are added
+            int nr = 0;
+            if (v16) reg[nr++] = &w[j & 15];
+            if (v15) reg[nr++] = &t[0];
+            if (v7) reg[nr++] = &w[(j - 7) & 15];
+            if (v2) reg[nr++] = &t[1];
+            // a four-term sum adds its first two terms (one may be the constant) first
+            if (k == 8) o = {{reg[0], c ? nullptr : reg[1], nullptr}, &t[2]};
+            else if (n == 4) o = {{&t[2], reg[nr - 1], reg[nr - 2]}, &w[j & 15]};
+            else o = {{reg[nr - 1], nr > 1 ? reg[nr - 2] : nullptr, nr > 2 ? reg[nr - 3] : nullptr}, &w[j & 15]};
+            if (RUN) {
+                uint32_t term[5] = {};
+                int m = 0;
+                if (c) term[m++] = job.kw[j];
+                if (v16) term[m++] = w[j & 15];
+                if (v15) term[m++] = t[0];
+                if (v7) term[m++] = w[(j - 7) & 15];
+                if (v2) term[m++] = t[1];
+                if (k == 8) t[2] = term[0] + term[1];
+                else w[j & 15] = n == 4 ? t[2] + term[2] + term[3] : term[0] + term[1] + term[2];
+            }
+        }
+    }
+    return o;
+}
+
+// The fourteen instructions of compression round i. h + K[i] + W[i], then t1, then the next a take h's place;
+// the next e takes d's.
+enum PowRoundOp { R_X, R_R1, R_R2, R_R3, R_CH, R_S1, R_T1, R_E, R_Q1, R_Q2, R_Q3, R_S0, R_MJ, R_A };
+
+template <int LAYOUT, int I, int OP, bool RUN>
+__host__ __device__ __forceinline__ PowOpRegs pow_round_op(const PowJobDev& job, PowSchedRegs& r) {
+    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
+    constexpr int i = I;
+    uint32_t(&s)[8] = r.s;
+    uint32_t(&u)[4] = r.u;
+    uint32_t(&q)[3] = r.q;
+    uint32_t &a = s[(0 - i) & 7], &b = s[(1 - i) & 7], &c = s[(2 - i) & 7], &d = s[(3 - i) & 7];
+    uint32_t &e = s[(4 - i) & 7], &f = s[(5 - i) & 7], &g = s[(6 - i) & 7], &h = s[(7 - i) & 7];
+    PowOpRegs o;
+    if constexpr (OP == R_X) {
+        o = {{&h, kinds.vec[i] ? &r.w[i & 15] : nullptr, nullptr}, &h};
+        if (RUN) h = kinds.vec[i] ? h + kSha256K[i] + r.w[i & 15] : h + job.kw[i];
+    } else if constexpr (OP == R_R1) {
+        o = {{&e, nullptr, nullptr}, &u[0]};
+        if (RUN) u[0] = P_ROTR(e, 6);
+    } else if constexpr (OP == R_R2) {
+        o = {{&e, nullptr, nullptr}, &u[1]};
+        if (RUN) u[1] = P_ROTR(e, 11);
+    } else if constexpr (OP == R_R3) {
+        o = {{&e, nullptr, nullptr}, &u[2]};
+        if (RUN) u[2] = P_ROTR(e, 25);
+    } else if constexpr (OP == R_CH) {
+        o = {{&e, &f, &g}, &u[3]};
+        if (RUN) u[3] = P_CH(e, f, g);
+    } else if constexpr (OP == R_S1) {
+        o = {{&u[2], &u[1], &u[0]}, &u[0]};
+        if (RUN) u[0] = P_XOR3(u[0], u[1], u[2]);
+    } else if constexpr (OP == R_T1) {
+        o = {{&u[0], &u[3], &h}, &h};
+        if (RUN) h = h + u[0] + u[3];
+    } else if constexpr (OP == R_E) {
+        if constexpr (i != 63) {  // nothing reads the last e
+            o = {{&h, &d, nullptr}, &d};
+            if (RUN) d = d + h;
+        }
+    } else if constexpr (OP == R_Q1) {
+        o = {{&a, nullptr, nullptr}, &q[0]};
+        if (RUN) q[0] = P_ROTR(a, 2);
+    } else if constexpr (OP == R_Q2) {
+        o = {{&a, nullptr, nullptr}, &q[1]};
+        if (RUN) q[1] = P_ROTR(a, 13);
+    } else if constexpr (OP == R_Q3) {
+        o = {{&a, nullptr, nullptr}, &q[2]};
+        if (RUN) q[2] = P_ROTR(a, 22);
+    } else if constexpr (OP == R_S0) {
+        o = {{&q[2], &q[1], &q[0]}, &q[0]};
+        if (RUN) q[0] = P_XOR3(q[0], q[1], q[2]);
+    } else if constexpr (OP == R_MJ) {
+        o = {{&a, &b, &c}, &q[1]};
+        if (RUN) q[1] = P_MAJ(a, b, c);
+    } else {
+        o = {{&q[1], &q[0], &h}, &h};
+        if (RUN) h = h + q[0] + q[1];
+    }
+    return o;
+}
+
+// f(integral_constant<int, B>) .. f(integral_constant<int, E - 1>) in order, unrolled by the front end
+template <int B, class F, int... I>
+__host__ __device__ __forceinline__ void pow_static_for(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, B + I>{}), ...);
+}
+template <int B, int E, class F>
+__host__ __device__ __forceinline__ void pow_static_for(F&& f) {
+    pow_static_for<B>(f, std::make_integer_sequence<int, (E > B ? E - B : 0)>{});
+}
+
+template <int LAYOUT, int D, bool TWO_PATH>
+struct PowOrder {
+    static constexpr int R0 = 10, FIRST = R0 + 4;  // first round whose whole state is nonce dependent
+    static constexpr int SLOTS = 24, STEPS = (64 - FIRST) * SLOTS;
+    static constexpr int kOnePath[14] = {R_X, R_R1, R_R2, R_R3, R_CH, R_S1, R_T1, R_Q1, R_E, R_Q2, R_Q3, R_S0, R_MJ, R_A};
+    static constexpr int kTwoPath[14] = {R_R1, R_Q1, R_R2, R_Q2, R_R3, R_Q3, R_CH, R_S1, R_X, R_S0, R_T1, R_MJ, R_E, R_A};
+    // step g of the pinned part: slot g % 24 of round FIRST + g / 24
+    static constexpr int round_of(int g) { return FIRST + g / SLOTS; }
+    static constexpr bool is_sched(int g) {
+        const int n = g % SLOTS;
+        return D == 0 ? n < 10 : (n < 20 && (n & 1));
+    }
+    static constexpr int sched_k(int g) { return D == 0 ? g % SLOTS : (g % SLOTS) / 2; }
+    static constexpr int round_op(int g) {
+        const int n = g % SLOTS, k = D == 0 ? n - 10 : n < 20 ? n / 2 : n - 10;
+        return TWO_PATH ? kTwoPath[k] : kOnePath[k];
+    }
+    static constexpr bool exists(int g) {
+        if (g < 0 || g >= STEPS) return false;
+        if (is_sched(g)) return pow_sched_op_exists(pow_word_kinds(LAYOUT), round_of(g) + D, sched_k(g));
+        return !(round_op(g) == R_E && round_of(g) == 63);
+    }
+    // v_alignbit_b32 and v_add3_u32 issue at 4.1 cycles, everything else here at 2.3 (docs/PERF.md)
+    static constexpr bool slow(int g) {
+        if (!exists(g)) return false;
+        const PowWordKinds kinds = pow_word_kinds(LAYOUT);
+        if (is_sched(g)) {
+            const int k = sched_k(g), j = round_of(g) + D;
+            if (k < 8) return (k & 3) < 2;
+            const int n = int(kinds.has_const[j]) + int(kinds.vec[j - 16]) + int(kinds.vec[j - 15]) +
+                          int(kinds.vec[j - 7]) + int(kinds.vec[j - 2]);
+            return k == 9 && n >= 3;
+        }
+        const int op = round_op(g);
+        if (op == R_X) return kinds.vec[round_of(g)];
+        return op == R_R1 || op == R_R2 || op == R_R3 || op == R_Q1 || op == R_Q2 || op == R_Q3 || op == R_T1 || op == R_A;
+    }
+    static constexpr bool rotate(int g) {
+        if (!exists(g)) return false;
+        if (is_sched(g)) return sched_k(g) < 8 && (sched_k(g) & 3) < 2;
+        const int op = round_op(g);
+        return op == R_R1 || op == R_R2 || op == R_R3 || op == R_Q1 || op == R_Q2 || op == R_Q3;
+    }
+    // FILL: an s_sleep 0, which does nothing and is no VALU instruction, goes in front of step g
+    //  1 if g is a rotate    2 if g is slow (a rotate or an add3)
+    static constexpr bool fill_before(int fill, int g) { return fill == 1 ? rotate(g) : fill == 2 ? slow(g) : false; }
+    static constexpr int next(int g) {  // the next step that has an instruction, or -1
+        if (g < 0) return -1;
+        for (int n = g + 1; n < STEPS; ++n)
+            if (exists(n)) return n;
+        return -1;
+    }
+    template <int G, bool RUN>
+    static __host__ __device__ __forceinline__ PowOpRegs op(const PowJobDev& job, PowSchedRegs& r) {
+        if constexpr (!exists(G)) return {};
+        else if constexpr (is_sched(G)) return pow_sched_op<LAYOUT, round_of(G) + D, sched_k(G), RUN>(job, r);
+        else return pow_round_op<LAYOUT, round_of(G), round_op(G), RUN>(job, r);
+    }
+};
+
+template <int LAYOUT, int D, bool TWO_PATH, int FILL>
+__host__ __device__ __forceinline__ uint32_t pow_h0_sched(const PowJobDev& job, uint32_t v) {
+    static_assert(LAYOUT == 2, "the pinned order is written for the 108-byte header");
+    static_assert(D >= 0 && D < 16, "W[i+D] takes the place of W[i+D-16], which round i must not need any more");
+    using O = PowOrder<LAYOUT, D, TWO_PATH>;
+    constexpr int R0 = O::R0, FIRST = O::FIRST;
+    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
+    PowSchedRegs r = {};
+    r.w[10] = v;
+    {
+        uint32_t(&s)[8] = r.s;
+        constexpr int i = R0 + 1;
+        s[(0 - i) & 7] = job.ca + v; s[(1 - i) & 7] = job.st[0]; s[(2 - i) & 7] = job.st[1]; s[(3 - i) & 7] = job.st[2];
+        s[(4 - i) & 7] = job.ce + v; s[(5 - i) & 7] = job.st[4]; s[(6 - i) & 7] = job.st[5]; s[(7 - i) & 7] = 0;
+    }
+    pow_static_for<16, FIRST + D>([&](auto j) {
+        pow_static_for<0, 10>([&](auto k) { pow_sched_op<LAYOUT, decltype(j)::value, decltype(k)::value, true>(job, r); });
+    });
+#pragma unroll
+    for (int i = R0 + 1; i < FIRST; ++i) {
+        uint32_t(&s)[8] = r.s;
+        uint32_t &a = s[(0 - i) & 7], &b = s[(1 - i) & 7], &c = s[(2 - i) & 7], &d = s[(3 - i) & 7];
+        uint32_t &e = s[(4 - i) & 7], &f = s[(5 - i) & 7], &g = s[(6 - i) & 7], &h = s[(7 - i) & 7];
+        const uint32_t x = kinds.vec[i] ? job.hk[i - R0 - 1] + r.w[i & 15] : job.hk[i - R0 - 1];
+        uint32_t t1 = x + P_BSIG1(e) + P_CH(e, f, g);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(t1));  // one add3 here, then e and a from it, as in pow_h0_pre
+#endif
+        const uint32_t t2 = P_BSIG0(a) + P_MAJ(a, b, c);
+        d = d + t1;
+        h = t1 + t2;
+    }
+    pow_static_for<0, O::STEPS>([&](auto gc) {
+        constexpr int g = decltype(gc)::value;
+        if constexpr (O::exists(g)) {
+            const PowOpRegs me = O::template op<g, true>(job, r);
+#if defined(__HIP_DEVICE_COMPILE__)
+            constexpr int g1 = O::next(g), g2 = O::next(g1);
+            const PowOpRegs n1 = O::template op<g1, false>(job, r), n2 = O::template op<g2, false>(job, r);
+            // An asm result must not be read by the very next instruction (s_nop), and the nonce word is live
+            // across iterations (redefining it would cost a copy). Redefining this instruction's own result as
+            // well keeps the optimiser from re-associating sums across the pinned instructions.
+            uint32_t* nin = n2.in[0];
+            if (nin == n1.out || n1.reads(nin) || nin == &r.w[10]) nin = nullptr;
+            uint32_t* own = n1.reads(me.out) ? nullptr : me.out;
+            if (nin != nullptr && own != nullptr && nin != own) asm volatile("" : "+v"(*nin), "+v"(*own));
+            else if (own != nullptr) asm volatile("" : "+v"(*own));
+            else if (nin != nullptr) asm volatile("" : "+v"(*nin) : "v"(*me.out));
+            else asm volatile("" ::"v"(*me.out));
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (O::fill_before(FILL, g1)) {
+                __builtin_amdgcn_s_sleep(0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#else
+            (void)me;
+#endif
+        }
+    });
+    return job.mid[0] + r.s[(0 - 64) & 7];
 }
 
 // Variant 2 (A/B evidence for the design note above): the same v2 search with the expanded message
@@ -251,6 +545,22 @@ __global__ __launch_bounds__(256, MIN_WAVES_PER_SIMD) void pow_search_pre_kernel
     uint32_t v = v_base + blockIdx.x * blockDim.x + threadIdx.x;
     for (uint32_t it = 0; it < iters; ++it, v += nthreads) {
         const uint32_t h0 = pow_h0_pre<LAYOUT>(job, v);
+        const bool hit = ((h0 ^ job.tword) & job.tmask) == 0 && ((h0 >> job.frac_shift) & 0xfu) < job.frac_limit;
+        if (__builtin_expect(hit, 0)) {
+            const uint32_t slot = atomicAdd(out_count, 1u);
+            if (slot < cap) out_words[slot] = v;
+        }
+    }
+}
+
+template <int D, bool TWO_PATH, int FILL, int MIN_WAVES_PER_SIMD>
+__global__ __launch_bounds__(256, MIN_WAVES_PER_SIMD) void pow_search_sched_kernel(PowJobDev job, uint32_t v_base, uint32_t iters,
+                                                               uint32_t* __restrict__ out_count,
+                                                               uint32_t* __restrict__ out_words, uint32_t cap) {
+    const uint32_t nthreads = gridDim.x * blockDim.x;
+    uint32_t v = v_base + blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint32_t it = 0; it < iters; ++it, v += nthreads) {
+        const uint32_t h0 = pow_h0_sched<2, D, TWO_PATH, FILL>(job, v);
         const bool hit = ((h0 ^ job.tword) & job.tmask) == 0 && ((h0 >> job.frac_shift) & 0xfu) < job.frac_limit;
         if (__builtin_expect(hit, 0)) {
             const uint32_t slot = atomicAdd(out_count, 1u);
@@ -365,10 +675,13 @@ static PowDeviceBuffers& pow_buffers(uint32_t cap) {
 //  4  host-precomputed uniforms in SGPRs (pow_h0_pre): 62 VGPRs, 103 SGPRs -> 7 waves/SIMD
 //  5  as 4 with the SGPR budget of 8 waves/SIMD: the compiler re-materialises K words with s_mov in the loop
 //     (SALU, no extra VALU), 61 VGPRs, no scratch
+//  6-9  variant 5's instructions in a pinned order (pow_h0_sched), W[i+2] produced during round i, 8 waves/SIMD:
+//     6  two-path rounds: next to no instruction follows its producer      7  rounds path after path
+//     8  as 7 with an s_sleep 0 in front of every rotate      9  as 7 with one in front of every rotate and add3
 //  0  the default, kPowDefaultVariant
-// v1 headers have the original loop (1-3) and the precomputed one (4, 5) only.
-constexpr int kPowDefaultVariant = 5;
-constexpr int kPowVariantCount = 6;
+// v1 headers have the original loop (1-3) and the precomputed one (4 and up) only.
+constexpr int kPowDefaultVariant = 9;
+constexpr int kPowVariantCount = 10;
 
 using PowKernelFn = void (*)(PowJobDev, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t);
 
@@ -382,11 +695,30 @@ static PowKernelFn pow_kernel_fn(bool v2, int variant) {
         case 2: return &pow_search_lds_kernel;
         case 4: return &pow_search_pre_kernel<2, 1>;
         case 5: return &pow_search_pre_kernel<2, 8>;
+        case 6: return &pow_search_sched_kernel<2, true, 0, 8>;
+        case 7: return &pow_search_sched_kernel<2, false, 0, 8>;
+        case 8: return &pow_search_sched_kernel<2, false, 1, 8>;
+        case 9: return &pow_search_sched_kernel<2, false, 2, 8>;
         default: return &pow_search_kernel<2, 1>;
     }
 }
 
 int pow_variant_count() { return kPowVariantCount; }
+
+// The same through the device function of kernel variant `variant` (the pinned orders exist for 108-byte
+// headers; every other variant and header is pow_h0_pre).
+uint32_t pow_job_h0_host(const PowJobHost& hj, uint32_t v, int variant) {
+    if (hj.header.size() != 108) return pow_job_h0_host(hj, v);
+    const PowJobDev job = make_pow_job(hj);
+    if (variant == 0) variant = kPowDefaultVariant;
+    switch (variant) {
+        case 6: return pow_h0_sched<2, 2, true, 0>(job, v);
+        case 7: return pow_h0_sched<2, 2, false, 0>(job, v);
+        case 8: return pow_h0_sched<2, 2, false, 1>(job, v);
+        case 9: return pow_h0_sched<2, 2, false, 2>(job, v);
+        default: return pow_h0_pre<2>(job, v);
+    }
+}
 
 // Grid = exactly the resident capacity of the chip (CUs x blocks/CU for this kernel's VGPR/SGPR use),
 // so every launch is one full "wave" of workgroups with no tail round.
