@@ -1,4 +1,5 @@
 """P-256: Python oracle, host C++ core and gfx950 batch kernels against each other."""
+import functools
 import hashlib
 import random
 
@@ -288,6 +289,11 @@ def test_on_curve_batch_matches_oracle(native):
             x, y = rng.randrange(1 << 256), rng.randrange(1 << 256)
         rows.append(x.to_bytes(32, 'little') + y.to_bytes(32, 'little'))
         want.append(1 if (x < o.P and y < o.P and o.is_on_curve(x, y)) else 0)
+    for row in _wrapped_rows():
+        x, y = int.from_bytes(row[:32], 'little'), int.from_bytes(row[32:], 'little')
+        rows.append(row)
+        want.append(1 if (x < o.P and y < o.P and o.is_on_curve(x, y)) else 0)
+    assert want[-6:] == [1, 0, 1, 0, 0, 0]
     got = native.p256_on_curve(b''.join(rows), False, 4)
     assert list(got) == want and sum(want) > 100
 
@@ -306,8 +312,15 @@ def test_on_curve_batch_gpu_matches_host(gpu):
         elif k % 2 == 0:
             y = o.P - y
         rows.append(x.to_bytes(32, 'little') + y.to_bytes(32, 'little'))
+    rows += _wrapped_rows()
     buf = b''.join(rows)
-    assert gpu.p256_on_curve(buf, True) == gpu.p256_on_curve(buf, False, 8)
+    got = gpu.p256_on_curve(buf, True)
+    assert got == gpu.p256_on_curve(buf, False, 8)
+    want = []
+    for row in rows:
+        x, y = int.from_bytes(row[:32], 'little'), int.from_bytes(row[32:], 'little')
+        want.append(1 if (x < o.P and y < o.P and o.is_on_curve(x, y)) else 0)
+    assert list(got) == want and want[-6:] == [1, 0, 1, 0, 0, 0] and 1000 < sum(want) < 4000
 
 
 @pytest.mark.gpu
@@ -339,6 +352,73 @@ def _off_curve_x(rng) -> int:
         rhs = (x ** 3 - 3 * x + o.B) % o.P
         if pow(rhs, (o.P - 1) // 2, o.P) != 1:
             return x
+
+
+@functools.lru_cache(maxsize=None)
+def _x_below_wrap() -> int:
+    """An x0 in [1, 2^256 - p) that is the abscissa of a curve point: x0 + p still fits 32 bytes, and a
+    check that reduced x before (or instead of) comparing it with p would accept it as x0."""
+    rng = random.Random(0xA55E)
+    while True:
+        x0 = rng.randrange(1, (1 << 256) - o.P)
+        if o.is_on_curve(x0, o.x_to_y(x0)):
+            return x0
+
+
+@functools.lru_cache(maxsize=None)
+def _point_y_below_wrap():
+    """A curve point (x0, y0) with y0 in [1, 2^256 - p), so that y0 + p fits 32 bytes. Draw y0, then solve
+    x^3 - 3x + b - y0^2 = 0: gcd(f, x^p - x) is the product of f's linear factors; taken when it is one."""
+    p = o.P
+    rng = random.Random(0xB0770)
+
+    def mulmod(u, v, c):  # u * v mod x^3 - 3x + c, coefficients low to high
+        w = [0] * 5
+        for i in range(3):
+            for j in range(3):
+                w[i + j] += u[i] * v[j]
+        for k in (4, 3):  # x^3 = 3x - c
+            w[k - 2] += 3 * w[k]
+            w[k - 3] -= c * w[k]
+        return [t % p for t in w[:3]]
+
+    while True:
+        y0 = rng.randrange(1, (1 << 256) - p)
+        c = (o.B - y0 * y0) % p
+        acc = [1, 0, 0]
+        for bit in bin(p)[2:]:
+            acc = mulmod(acc, acc, c)
+            if bit == '1':
+                acc = mulmod(acc, [0, 1, 0], c)
+        g = [acc[0], (acc[1] - 1) % p, acc[2]]  # x^p - x mod f, degree <= 2
+        f = [c, p - 3, 0, 1]
+        while any(g):  # Euclid
+            while g[-1] == 0:
+                g.pop()
+            inv = pow(g[-1], -1, p)
+            while len(f) >= len(g):
+                k = f[-1] * inv % p
+                for i in range(len(g)):
+                    f[len(f) - len(g) + i] = (f[len(f) - len(g) + i] - k * g[i]) % p
+                f.pop()
+            f, g = g, f + [0] * (not f)
+        if len(f) == 2:
+            x0 = -f[0] * pow(f[1], -1, p) % p
+            assert o.is_on_curve(x0, y0) and y0 + p < 1 << 256
+            return x0, y0
+
+
+def _wrapped_rows():
+    """64-byte addresses whose x or y is a curve point's coordinate plus p, each behind the point itself:
+    (x0, y0), (x0 + p, y0) for a small x0; (x1, y1), (x1, y1 + p), (x1 + p, y1 + p) where it fits, and
+    (x0 + p, y1 + p), for a small y1. Only the comparison with p rejects them."""
+    p = o.P
+    x0 = _x_below_wrap()
+    y0 = o.x_to_y(x0)
+    x1, y1 = _point_y_below_wrap()
+    assert o.is_on_curve(x0, y0) and o.is_on_curve(x1, y1) and max(x0, y1) + p < 1 << 256
+    pairs = [(x0, y0), (x0 + p, y0), (x1, y1), (x1, y1 + p), (x1 + p if x1 + p < 1 << 256 else x1, y1 + p), (x0 + p, y1 + p)]
+    return [x.to_bytes(32, 'little') + y.to_bytes(32, 'little') for x, y in pairs]
 
 
 def _fused_block(seed, bad_out=False, bad_signer=False):

@@ -19,7 +19,7 @@ import pytest
 from upow_amd.ops import p256 as op
 from upow_amd.utils import p256 as o
 
-from test_p256 import _off_curve_x
+from test_p256 import _off_curve_x, _x_below_wrap
 
 N = o.N
 M64 = (1 << 64) - 1
@@ -272,6 +272,9 @@ def _decompress_edges():
     rng = random.Random(77)
     rows = [(42, 0), (43, 0)]
     rows += [(pre, x) for x in (o.P - 1, o.P, o.P + 1, (1 << 256) - 1) for pre in (42, 43)]
+    x0 = _x_below_wrap()
+    assert o.is_on_curve(x0, o.x_to_y(x0)) and o.P <= x0 + o.P < 1 << 256
+    rows += [(42, x0 + o.P), (43, x0 + o.P)]
     rows += [(42 + (k & 1), _off_curve_x(rng)) for k in range(3)]
     for _ in range(4):
         q = _pub(rng.randrange(1, N))
