@@ -338,6 +338,65 @@ PYBIND11_MODULE(_native, m) {
         return py::bytes(out);
     }, py::arg("keys_be"), py::arg("digests"), py::arg("threads") = 8);
 
+    // The batched signer's shared core (csrc/p256_sign.h, not constant-time): on the GPU (gpu=True: one lane
+    // per item) or the same code on the host pool. Same failure contract as the _batch forms above: a key
+    // outside [1, n-1] leaves its 64 output bytes zero. The keys are read in place, not copied.
+    auto bytes32_arg = [](const py::buffer& b, const char* what, int64_t& n) {
+        py::buffer_info bi = b.request();
+        const int64_t nb = bi.size * bi.itemsize;
+        if (nb % 32) throw std::invalid_argument(std::string(what) + " must be n x 32 bytes");
+        n = nb / 32;
+        return static_cast<const uint8_t*>(bi.ptr);
+    };
+    m.def("p256_pubkey_many", [bytes32_arg](py::buffer keys_be, bool gpu, int threads) -> py::bytes {
+        int64_t n = 0;
+        const uint8_t* kp = bytes32_arg(keys_be, "keys", n);
+        std::string out(size_t(n) * 64, '\0'), ok(size_t(n), '\0');
+        {
+            py::gil_scoped_release rel;
+            auto* o = reinterpret_cast<uint8_t*>(&out[0]);
+            auto* f = reinterpret_cast<uint8_t*>(&ok[0]);
+            if (gpu) p256_pubkey_gpu(kp, n, o, f);
+            else p256_pubkey_many_host(kp, n, o, f, threads);
+        }
+        return py::bytes(out);
+    }, py::arg("keys_be"), py::arg("gpu"), py::arg("threads") = 8);
+
+    m.def("p256_sign_many", [bytes32_arg](py::buffer keys_be, py::buffer digests, bool gpu, int threads) -> py::bytes {
+        int64_t n = 0, nd = 0;
+        const uint8_t* kp = bytes32_arg(keys_be, "keys", n);
+        const uint8_t* hp = bytes32_arg(digests, "digests", nd);
+        if (nd != n) throw std::invalid_argument("need as many digests as keys");
+        std::string out(size_t(n) * 64, '\0'), ok(size_t(n), '\0');
+        {
+            py::gil_scoped_release rel;
+            auto* o = reinterpret_cast<uint8_t*>(&out[0]);
+            auto* f = reinterpret_cast<uint8_t*>(&ok[0]);
+            if (gpu) p256_sign_gpu(kp, hp, n, o, f);
+            else p256_sign_many_host(kp, hp, n, o, f, threads);
+        }
+        return py::bytes(out);
+    }, py::arg("keys_be"), py::arg("digests"), py::arg("gpu"), py::arg("threads") = 8);
+
+    m.def("p256_rfc6979_candidates", [](py::bytes key_be, py::bytes digest, int count, bool gpu) -> py::bytes {
+        const std::string d = key_be, h = digest;
+        if (d.size() != 32 || h.size() != 32) throw std::invalid_argument("need 32-byte key and digest");
+        if (count < 0 || count > 64) throw std::invalid_argument("count must be in [0, 64]");
+        std::string out(size_t(count) * 32, '\0');
+        {
+            py::gil_scoped_release rel;
+            auto* o = reinterpret_cast<uint8_t*>(&out[0]);
+            const auto* kp = reinterpret_cast<const uint8_t*>(d.data());
+            const auto* hp = reinterpret_cast<const uint8_t*>(h.data());
+            if (gpu) p256_candidates_gpu(kp, hp, count, o);
+            else p256_candidates_host(kp, hp, count, o);
+        }
+        return py::bytes(out);
+    }, py::arg("key_be"), py::arg("digest"), py::arg("count"), py::arg("gpu"),
+       "FOR TESTS ONLY: this returns nonces, and a nonce reveals the private key of the signature made with it. "
+       "The first `count` RFC 6979 HMAC_DRBG candidates (32 bytes big-endian each) for key and digest, accepted "
+       "or not, from the batched signer's shared core: the only way to exercise the DRBG's retry update.");
+
     auto recs_arg = [](py::buffer b, int64_t& n) {
         py::buffer_info bi = b.request();
         const int64_t nb = bi.size * bi.itemsize;

@@ -65,6 +65,8 @@ void rccl_vote_destroy(int64_t h, bool abort);
 std::vector<double> rccl_vote_stats(int64_t h);  // votes, then seconds in the all-gather, copy, event enqueues
 // entries [first, first + count) of the device's 16-bit fixed-base window table (x, y little-endian each)
 std::vector<uint8_t> p256_g16_entries(int64_t first, int64_t count);
+// that table on the current device (a device pointer to 16 x 65,536 x {x[8], y[8]}), built on first use
+const void* p256_g16_table_device();
 std::vector<uint8_t> p256_verify_gpu(const uint8_t* items, int64_t n);
 void p256_decompress_host(const uint8_t* in33, int64_t n, uint8_t* out64, uint8_t* ok);
 void p256_decompress_gpu(const uint8_t* in33, int64_t n, uint8_t* out64, uint8_t* ok);
@@ -79,6 +81,19 @@ void p256_on_curve_gpu(const uint8_t* xy64, int64_t n, uint8_t* ok);
 void set_node_device_native(int dev);
 bool p256_pubkey(const uint8_t d_be[32], uint8_t out_le[64]);
 bool p256_sign(const uint8_t d_be[32], const uint8_t digest[32], uint8_t r_le[32], uint8_t s_le[32]);
+// K15 batched (core: csrc/p256_sign.h, not constant-time): n x 32-byte big-endian keys (and n x 32-byte SHA-256
+// digests) -> n x 64 bytes x | y (r | s) little-endian and ok[n]; a key outside [1, n - 1] gets 64 zero bytes
+// and ok = 0. _many_host: the kernels' core on the host pool; _gpu: one H2D, one launch, one D2H on the node
+// stream, the device and pinned copies of the keys overwritten before return (csrc/p256_sign.hip)
+void p256_pubkey_many_host(const uint8_t* keys_be, int64_t n, uint8_t* out_le, uint8_t* ok, int threads);
+void p256_sign_many_host(const uint8_t* keys_be, const uint8_t* digests, int64_t n, uint8_t* rs_le, uint8_t* ok,
+                         int threads);
+void p256_pubkey_gpu(const uint8_t* keys_be, int64_t n, uint8_t* out_le, uint8_t* ok);
+void p256_sign_gpu(const uint8_t* keys_be, const uint8_t* digests, int64_t n, uint8_t* rs_le, uint8_t* ok);
+// test hooks: the first `count` RFC 6979 candidates (32 bytes big-endian each, accepted or not) from the shared
+// core on one host thread / one GPU thread. They leak the nonce.
+void p256_candidates_host(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
+void p256_candidates_gpu(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
 
 // ---------------------------------------------------------------- HBM UTXO index (K7/K8/K9)
 // key records: 40 bytes {txid[32] raw, uint32 index, uint32 tag}

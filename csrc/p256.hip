@@ -44,9 +44,6 @@ using namespace p256;
 // ------------------------------------------------------------------------------------------------
 // fixed-base table (host-built once, uploaded once per device)
 // ------------------------------------------------------------------------------------------------
-static constexpr int kGWin = 32;   // byte windows
-static constexpr int kGEnt = 256;  // entry 0 unused
-
 static std::once_flag g_tab_once;
 static std::vector<aff> g_tab;  // [kGWin][kGEnt]
 
@@ -110,15 +107,6 @@ void p256_scalar_inv_mont_host(uint64_t out[4], const uint64_t s[4]) {
     std::memcpy(a.v, s, 32);
     const fe r = sc_inv_safegcd_mont(a);
     std::memcpy(out, r.v, 32);
-}
-
-UPOW_HD jac mul_g(const fe& k, const aff* tab) {
-    jac acc = jac_inf();
-    for (int j = 0; j < kGWin; ++j) {
-        const uint32_t b = fe_byte(k, j);
-        if (b) acc = jac_madd(acc, tab[j * kGEnt + b]);
-    }
-    return acc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -726,6 +714,10 @@ std::vector<uint8_t> p256_g16_entries(int64_t first, int64_t count) {
     node_d2h(out.data(), d + first, out.size(), "d2h gtab16");
     return out;
 }
+
+// the current device's 16-bit-window table for the signing kernels' host entry points (csrc/p256_sign.hip);
+// call after node_device_enter()
+const void* p256_g16_table_device() { return device_g16_table(); }
 
 // ------------------------------------------------------------------------------------------------
 // host API

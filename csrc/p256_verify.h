@@ -83,6 +83,19 @@ struct BoothW5 {
 };
 static constexpr int kBoothWindows = 52;
 
+// The host's k*G: 32 byte windows over T[j][b] = b * 256^j * G (32 x 256 affine points, entry 0 unused; built
+// once by csrc/p256.hip, p256_g_table_host)
+static constexpr int kGWin = 32;
+static constexpr int kGEnt = 256;
+UPOW_HD jac mul_g(const fe& k, const aff* tab) {
+    jac acc = jac_inf();
+    for (int j = 0; j < kGWin; ++j) {
+        const uint32_t b = fe_byte(k, j);
+        if (b) acc = jac_madd(acc, tab[j * kGEnt + b]);
+    }
+    return acc;
+}
+
 // The GPU kernels' u1*G: 16 windows of 16 bits over T16[j][b] = b * 2^(16 j) * G (16 x 65,536 affine
 // points, 64 MiB in HBM, built on the device from the byte-window table: build_g16_kernel). Half the mixed
 // additions of the byte windows (a lane's quarter is 4 windows: 3 additions instead of 7); the table

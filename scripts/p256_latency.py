@@ -3,7 +3,8 @@
 Wall time per launch (H2D of 1.3 MB records + kernel + D2H of the status bytes), median of 7; the
 kernel-only time comes from a rocprofv3 --kernel-trace run of this script. Knobs read per call:
 UPOW_P256_VARIANT (kernel variant), UPOW_P256_SPW (signatures per 64-lane wave). A config is
-variant:spw[:n], n = signatures per launch (default all 8,300)."""
+variant:spw[:n], n = signatures per launch (default all 8,300). With --distinct-keys the 8,300 records come
+from 8,300 fresh keys (op.sign_records) instead of 64 keys in turn."""
 import hashlib
 import json
 import os
@@ -18,14 +19,19 @@ from upow_amd.ops import p256 as op  # noqa: E402
 
 lib()
 rng = random.Random(1)
-keys = [rng.randrange(1, op.oracle.N) for _ in range(64)]
-pubs = [op.public_key(k) for k in keys]
-recs = []
-for i in range(8300):
-    msg = rng.randbytes(200)
-    recs.append(op.record(pubs[i % 64], op.sign(msg, keys[i % 64]), hashlib.sha256(msg).digest()))
+args = [x for x in sys.argv[1:] if x != '--distinct-keys']
+if len(args) != len(sys.argv) - 1:
+    keys = [rng.randrange(1, op.oracle.N) for _ in range(8300)]
+    recs = [bytes(r) for r in op.sign_records(keys, [rng.randbytes(32) for _ in range(8300)])]
+else:
+    keys = [rng.randrange(1, op.oracle.N) for _ in range(64)]
+    pubs = [op.public_key(k) for k in keys]
+    recs = []
+    for i in range(8300):
+        msg = rng.randbytes(200)
+        recs.append(op.record(pubs[i % 64], op.sign(msg, keys[i % 64]), hashlib.sha256(msg).digest()))
 base = b''.join(recs)
-configs = [c.split(':') for c in (','.join(sys.argv[1:]).split(',') if len(sys.argv) > 1 else ['1:64', '1:32', '1:16'])]
+configs = [c.split(':') for c in (','.join(args).split(',') if args else ['1:64', '1:32', '1:16'])]
 out = {}
 rec_len = len(recs[0])
 for cfg in configs:

@@ -1,4 +1,4 @@
-"""P-256 front end: single sign/verify (host C++) and batched verify/decompress (gfx950 kernels).
+"""P-256 front end: single sign/verify (host C++) and batched verify/decompress/keygen/sign (gfx950 kernels).
 
 Batch record layout (160 B, little-endian like the wire format): ``qx | qy | r | s | e`` where ``e``
 is the SHA-256 digest of the signed message (big-endian, as hashed). Status codes: 1 valid,
@@ -76,6 +76,74 @@ def verify(sig: Tuple[int, int], msg: Union[str, bytes], q: Point) -> bool:
     return bool(st == VALID)
 
 
+# ---------------------------------------------------------------------------------------------- batched signing
+# below this many items a batch of keys or signatures runs on host threads; UPOW_P256_SIGN_GPU_MIN (read per
+# call) overrides it. Measured by scripts/p256_sign_throughput.py on an MI355X (docs/PERF.md "P-256 signing"):
+# the smallest measured n at which the GPU beats 16 host threads end to end by >= 20 % for both functions is
+# the smallest n measured, 256 (signing 1.66x, keys 1.24x; 5.2x / 4.1x at 1,024)
+SIGN_GPU_MIN = 256
+
+
+def _keys_be(keys: Sequence[int]) -> bytes:
+    for i, d in enumerate(keys):
+        if not 1 <= int(d) < oracle.N:
+            raise ValueError(f'private key {i} out of range')
+    return b''.join(int(d).to_bytes(32, 'big') for d in keys)
+
+
+def _sign_on_gpu(n: int, device: Optional[str]) -> bool:
+    if device is None:
+        return gpu_available() and n >= int(os.environ.get('UPOW_P256_SIGN_GPU_MIN', SIGN_GPU_MIN))
+    if device not in ('gpu', 'cpu'):
+        raise ValueError("device must be 'gpu', 'cpu' or None")
+    return device == 'gpu'
+
+
+def _rows64(out: bytes, n: int, what: str) -> np.ndarray:
+    rows = np.frombuffer(out, dtype=np.uint8).reshape(n, 64)
+    bad = np.flatnonzero(~rows.any(axis=1))
+    if bad.size:  # keys were range-checked: a failed candidate loop (or a device that returned nothing)
+        raise ValueError(f'{what} failed for item {int(bad[0])}')
+    return rows
+
+
+def public_keys(keys: Sequence[int], device: Optional[str] = None) -> np.ndarray:
+    """Public keys of n private keys -> uint8 array (n, 64), x | y little-endian. Runs the batched signer's
+    core (csrc/p256_sign.h; not constant-time: bulk work on a trusted machine) on the GPU or on host threads.
+    ``ValueError`` names the first key outside [1, n-1]."""
+    n = len(keys)
+    if n == 0:
+        return np.zeros((0, 64), dtype=np.uint8)
+    out = lib().p256_pubkey_many(_keys_be(keys), _sign_on_gpu(n, device), max(1, min(cpu_budget(), 16)))
+    return _rows64(out, n, 'key derivation')
+
+
+def sign_digests(keys: Sequence[int], digests: Sequence[bytes], device: Optional[str] = None) -> np.ndarray:
+    """RFC 6979 signatures of n SHA-256 digests, key i over digest i -> uint8 array (n, 64), r | s
+    little-endian (no low-s normalisation, like :func:`sign`). Same core and caveat as :func:`public_keys`."""
+    n = len(keys)
+    if len(digests) != n:
+        raise ValueError('need one digest per key')
+    if n == 0:
+        return np.zeros((0, 64), dtype=np.uint8)
+    dig = b''.join(bytes(h) for h in digests)
+    if len(dig) != 32 * n:
+        raise ValueError('digests must be 32 bytes each')
+    out = lib().p256_sign_many(_keys_be(keys), dig, _sign_on_gpu(n, device), max(1, min(cpu_budget(), 16)))
+    return _rows64(out, n, 'signing')
+
+
+def sign_records(keys: Sequence[int], digests: Sequence[bytes], device: Optional[str] = None) -> np.ndarray:
+    """Ready-made verify records ``qx | qy | r | s | e`` -> uint8 array (n, 160) for :func:`verify_records`."""
+    n = len(keys)
+    recs = np.empty((n, 160), dtype=np.uint8)
+    recs[:, 64:128] = sign_digests(keys, digests, device)
+    recs[:, :64] = public_keys(keys, device)
+    if n:
+        recs[:, 128:] = np.frombuffer(b''.join(bytes(h) for h in digests), dtype=np.uint8).reshape(n, 32)
+    return recs
+
+
 # ---------------------------------------------------------------------------------------------- admission
 # reference: every /push_tx verifies its signatures one at a time on the node's event loop
 # (transaction_input.py:100-109 via fastecdsa). Inside an admission context (utils/coalesce.py) the
@@ -125,4 +193,5 @@ def decompress(addresses33: Sequence[bytes], device: Optional[str] = None):
     return res
 
 
-__all__ = ['public_key', 'sign', 'verify', 'verify_async', 'verify_records', 'decompress', 'record', 'EcdsaError', 'oracle']
+__all__ = ['public_key', 'sign', 'verify', 'verify_async', 'verify_records', 'decompress', 'record', 'EcdsaError', 'oracle',
+           'public_keys', 'sign_digests', 'sign_records', 'SIGN_GPU_MIN']

@@ -10,6 +10,10 @@ tables, one JSON line per address, straight from the UTXO index (on a GPU node O
 pass over the HBM table for all of them, K14).
 ``python -m upow_amd.tools materialise --db <rankN ledger>``: bring a lean cluster follower's SQL tables to its
 tip from its op log (ledger/lean.py); every other command does this first when the ledger has an op log.
+``python -m upow_amd.tools sign-batch --keys F --digests F --out F [--device gpu|cpu]``: bulk RFC 6979 signing
+(K15 batched, ops/p256.py sign_digests; not constant-time, for a machine the operator trusts). F are raw files:
+32-byte big-endian private keys, 32-byte SHA-256 digests, and 64-byte ``r | s`` little-endian out. One JSON
+line with counts and seconds; a key outside [1, n-1] gets 64 zero bytes and exit status 1.
 """
 from __future__ import annotations
 
@@ -93,15 +97,52 @@ async def rebuild_utxo(path: str = None):
     return len(outputs)
 
 
+def sign_batch(keys_path: str, digests_path: str, out_path: str, device: str = None) -> dict:
+    """Sign digest i of ``digests_path`` with key i of ``keys_path`` into ``out_path``; the result line of the
+    ``sign-batch`` command. Nothing read from the key file is printed or returned."""
+    import time
+
+    import numpy as np
+
+    from .ops import p256
+    from .utils.cpus import cpu_budget
+    with open(keys_path, 'rb') as f:
+        keys = f.read()
+    with open(digests_path, 'rb') as f:
+        digests = f.read()
+    if len(keys) % 32 or len(digests) != len(keys):
+        raise SystemExit('sign-batch: need n x 32 bytes of keys and as many of digests')
+    n = len(keys) // 32
+    gpu = p256._sign_on_gpu(n, device)
+    t = time.perf_counter()
+    out = p256.lib().p256_sign_many(keys, digests, gpu, max(1, min(cpu_budget(), 16))) if n else b''
+    seconds = time.perf_counter() - t
+    with open(out_path, 'wb') as f:
+        f.write(out)
+    failed = np.flatnonzero(~np.frombuffer(out, dtype=np.uint8).reshape(n, 64).any(axis=1))
+    return {'signatures': n - int(failed.size), 'failed': int(failed.size),
+            'first_failed': int(failed[0]) if failed.size else None, 'device': 'gpu' if gpu else 'cpu',
+            'seconds': round(seconds, 6)}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('command', choices=['rebuild-utxo', 'utxo-hash', 'snapshot', 'verify-utxo', 'address-utxos',
-                                        'materialise'])
+                                        'materialise', 'sign-batch'])
     ap.add_argument('address', nargs='*')
     ap.add_argument('--db', default=None)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--keys', default=None)
+    ap.add_argument('--digests', default=None)
+    ap.add_argument('--device', choices=['gpu', 'cpu'], default=None)
     a = ap.parse_args(argv)
-    if a.command == 'address-utxos':
+    if a.command == 'sign-batch':
+        if not (a.keys and a.digests and a.out):
+            ap.error('sign-batch needs --keys, --digests and --out')
+        res = sign_batch(a.keys, a.digests, a.out, a.device)
+        print(json.dumps(res))
+        return 1 if res['failed'] else 0
+    elif a.command == 'address-utxos':
         if not a.address:
             ap.error('address-utxos needs an ADDRESS')
         for res in asyncio.run(address_utxos_many(a.address, a.db)):  # one JSON line per address
