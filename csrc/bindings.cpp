@@ -576,6 +576,16 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(qidx, py::bytes(reinterpret_cast<const char*>(r.recs.data()), r.recs.size()),
                               py::bytes(reinterpret_cast<const char*>(r.payload.data()), r.payload.size()), totals);
     }, py::arg("h"), py::arg("addrs"), py::arg("lens"), py::arg("tag_masks"), py::arg("stake_sels"));
+    // holders report: (112-byte owner records, owners, outputs, skipped, totals u64[8]); top -1 = every owner
+    m.def("utxo_owner_totals", [](int64_t h, int64_t top, uint32_t by_mask, uint32_t log2_groups, uint32_t tag_bits) {
+        OwnerTotalsOut r;
+        { py::gil_scoped_release rel; utxo_owner_totals(h, top, by_mask, log2_groups, tag_bits, r); }
+        py::array_t<uint64_t> totals(8);
+        std::memcpy(totals.mutable_data(), r.totals, sizeof r.totals);
+        return py::make_tuple(py::bytes(reinterpret_cast<const char*>(r.recs.data()), r.recs.size()), r.owners,
+                              r.outputs, r.skipped, totals);
+    }, py::arg("h"), py::arg("top") = -1, py::arg("by_mask") = 0x81u, py::arg("log2_groups") = 0u,
+       py::arg("tag_bits") = 32u);
     // test hooks: (home slot u32[n], K10 fingerprint u64[n]) of key records; the table's raw 48-byte slots
     m.def("utxo_debug_hashes", [recs_arg](py::buffer recs, uint32_t log2_cap) {
         int64_t n; const uint8_t* p = recs_arg(recs, n);

@@ -128,6 +128,21 @@ struct AddressBatchOut {
 };
 void utxo_address_scan_batch(int64_t h, const uint8_t* addrs, const uint32_t* lens, const uint32_t* tag_masks,
                              const uint32_t* stake_sels, int64_t n, AddressBatchOut& out);
+// Holders report: every owner's totals in one table pass (a hash aggregation by canonical 33-byte owner key,
+// the 33- and 64-byte forms of a key folded). `recs` are 112-byte records {key[33], pad[7], u32 outputs, u32
+// outputs in the 64-byte form, u64 sums[8]} in no particular order: every owner when top is -1, none when it
+// is 0, else every owner whose metric (sum of the by_mask columns mod 2^64) is at least the top-th greatest,
+// boundary ties included, so at least min(top, owners) of them. The counts and totals are over the whole set.
+// log2_groups (0: as many slots as the table; else in [4, 31]) and tag_bits (in [0, 32]) size the scratch group
+// table and mask its fingerprint tag: test levers, not set by the node. Entries that find no group slot make
+// the call throw std::runtime_error with their count; the table is only read.
+struct OwnerTotalsOut {
+    std::vector<uint8_t> recs;
+    uint64_t owners = 0, outputs = 0, skipped = 0;
+    uint64_t totals[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+void utxo_owner_totals(int64_t h, int64_t top, uint32_t by_mask, uint32_t log2_groups, uint32_t tag_bits,
+                       OwnerTotalsOut& out);
 
 // whole-block input pass: lookup (K7) + duplicate candidates (K10) + per-tx fees (K11) in one round trip
 // Outputs of the whole-block input pass, written in place (the caller's arrays: no intermediate copies)

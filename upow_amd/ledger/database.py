@@ -3132,6 +3132,33 @@ class Database:
                 out[a] += await self._pending_regular_income(a, pending)
         return out
 
+    async def get_owner_totals(self, top: Optional[int] = None, by: Sequence[str] = ('spendable', 'stake')):
+        """Holders report: ``(rows, summary)`` from one pass over the UTXO index (``UtxoIndex.owner_totals``;
+        on a GPU node a hash aggregation over the HBM table). One row per public key, both address forms
+        folded: ``address`` (compressed base58), ``outputs``, ``outputs_full_form`` (how many are stored in
+        the 64-byte form), ``spendable``, ``stake`` and ``tables`` (the six governance columns), amounts as
+        Decimals. ``top=None``: every holder, ascending by key bytes; ``top=N``: the N greatest by the sum
+        of the ``by`` columns (names of ``OWNER_COLUMNS``), ties by key. ``summary``: ``holders``,
+        ``outputs``, ``skipped`` and per-column ``totals`` over the whole set, whatever ``top`` is.
+        It always reads the index and there is no SQL fallback: an entry indexed without its payload cannot be
+        attributed and is counted in ``skipped``. Pending transactions are not considered."""
+        from .utxo import OWNER_COLUMNS
+        cols = []
+        for name in by:
+            if name not in OWNER_COLUMNS:
+                raise ValueError(f'no owner column {name!r}: columns are {", ".join(OWNER_COLUMNS)}')
+            cols.append(OWNER_COLUMNS.index(name))
+        owners, info = self.utxo.owner_totals(top, cols)
+        rows = []
+        for o in owners:
+            amounts = {c: Decimal(int(v)) / SMALLEST for c, v in zip(OWNER_COLUMNS, o['sums'])}
+            rows.append({'address': codec.bytes_to_string(bytes(o['key'])), 'outputs': int(o['outputs']),
+                         'outputs_full_form': int(o['outputs_full']), 'spendable': amounts.pop('spendable'),
+                         'stake': amounts.pop('stake'), 'tables': amounts})
+        summary = {'holders': info['owners'], 'outputs': info['outputs'], 'skipped': info['skipped'],
+                   'totals': {c: Decimal(int(v)) / SMALLEST for c, v in zip(OWNER_COLUMNS, info['totals'])}}
+        return rows, summary
+
     async def get_pending_stake_transaction(self, address: str):
         search = self._search(address)
         out = []

@@ -67,6 +67,76 @@ def make_payload(amounts: Sequence[Optional[int]], addrs: Sequence[Optional[byte
 
 Outpoint = Tuple[str, int]
 
+# Holders report (``UtxoIndex.owner_totals``): one record per owner. An owner is a public key: ``key`` is the
+# canonical 33 bytes ``42|43 || x`` that the 33-byte and the 64-byte form of an address both fold to (the rule of
+# csrc/txcodec.cpp input_address_strings). ``sums`` are the amount sums modulo 2^64 in OWNER_COLUMNS order: column
+# = table tag for tags 1..6; tag 0 is column 7 when staked, else column 0.
+OWNER_COLUMNS = ('spendable', 'inode_registration_output', 'validator_registration_output',
+                 'validators_voting_power', 'delegates_voting_power', 'validators_ballot', 'inodes_ballot', 'stake')
+OWNER_DTYPE = np.dtype([('key', 'u1', (33,)), ('pad', 'u1', (7,)), ('outputs', '<u4'), ('outputs_full', '<u4'),
+                        ('sums', '<u8', (8,))])
+assert OWNER_DTYPE.itemsize == 112
+_KEY33 = np.dtype((np.void, 33))
+
+
+def _by_mask(top, by) -> int:
+    """Argument check of ``owner_totals``: the ``by`` columns as a bit mask."""
+    if top is not None and (not isinstance(top, (int, np.integer)) or top < 0):
+        raise ValueError('top is None or a count >= 0')
+    mask = 0
+    for c in by:
+        if not isinstance(c, (int, np.integer)) or not 0 <= c < len(OWNER_COLUMNS):
+            raise ValueError(f'no owner column {c!r}: columns are 0..{len(OWNER_COLUMNS) - 1}')
+        mask |= 1 << int(c)
+    if not mask:
+        raise ValueError('by names at least one column')
+    return mask
+
+
+def owner_totals_of(recs: np.ndarray, pay: np.ndarray):
+    """Group live entries (packed records + payloads, as ``records_payload`` gives them) by owner key:
+    (OWNER_DTYPE records ascending by key, info). What the host backends run, and the reference the HBM
+    aggregation is tested against."""
+    tags = np.ascontiguousarray(recs[:, 36:40]).view('<u4').ravel() if len(recs) else np.zeros(0, np.uint32)
+    ok = ((pay['len'] == 33) | (pay['len'] == 64)) & (tags <= 6)
+    p, t = pay[ok], tags[ok]
+    n = len(p)
+    full = p['len'] == 64
+    addr = p['addr'].reshape(n, 64)
+    key = np.empty((n, 33), dtype=np.uint8)
+    key[:, 0] = np.where(full, 42 + (addr[:, 32] & 1), np.where(addr[:, 0] == 43, 43, 42))
+    key[:, 1:] = np.where(full[:, None], addr[:, :32], addr[:, 1:33])
+    col = np.where((t == 0) & ((p['flags'] & FLAG_STAKE) != 0), 7, t).astype(np.intp)
+    uniq, inv = np.unique(key.view(_KEY33).ravel(), return_inverse=True)
+    inv = inv.ravel()
+    owners = np.zeros(len(uniq), dtype=OWNER_DTYPE)
+    owners['key'] = uniq.view(np.uint8).reshape(-1, 33)
+    sums = np.zeros((len(uniq), 8), dtype=np.uint64)
+    np.add.at(sums, (inv, col), p['amount'])  # uint64: modulo 2^64
+    owners['sums'] = sums
+    owners['outputs'] = np.bincount(inv, minlength=len(uniq))
+    owners['outputs_full'] = np.bincount(inv[full], minlength=len(uniq))
+    info = {'owners': len(uniq), 'outputs': n, 'skipped': int(len(pay) - n), 'totals': sums.sum(axis=0, dtype=np.uint64)}
+    return _owners_in_order(owners, None, 0xff), info
+
+
+def _owners_in_order(owners: np.ndarray, top: Optional[int], by_mask: int) -> np.ndarray:
+    """Owner records ascending by key; with ``top``, the first ``top`` in (metric descending, key ascending)
+    order, the metric being the sum of the ``by_mask`` columns modulo 2^64."""
+    if len(owners) > 1:
+        key = np.ascontiguousarray(owners['key'])
+        # the first eight bytes as one big-endian word order random keys; equal words: all 33 bytes decide
+        head = np.ascontiguousarray(key[:, :8]).view('>u8').ravel()
+        order = np.argsort(head, kind='stable')
+        if (head[order][1:] == head[order][:-1]).any():
+            order = np.argsort(key.view(_KEY33).ravel(), kind='stable')
+        owners = owners[order]
+    if top is None:
+        return owners
+    cols = [c for c in range(8) if (by_mask >> c) & 1]
+    metric = owners['sums'][:, cols].sum(axis=1, dtype=np.uint64)
+    return owners[np.argsort(~metric, kind='stable')[:top]]  # ~m = 2^64 - 1 - m: descending, ties by key
+
 
 def pack_records(keys: Sequence[Outpoint], tags=None) -> np.ndarray:
     """40-byte records {txid raw 32 B, u32 index, u32 tag} for the native table."""
@@ -168,6 +238,10 @@ class _HostBackend:
         pay = np.frombuffer(b''.join(self.p.get(k, bytes(80)) for k in keys), dtype=PAYLOAD_DTYPE)
         return pack_records(keys, [self.d[k] for k in keys]), pay
 
+    def owner_totals(self, top, by_mask, log2_groups=0, tag_bits=32):
+        """Every owner's record and the whole-set info, grouped on the host (``owner_totals_of``)."""
+        return owner_totals_of(*self.records_payload())
+
     def __len__(self):
         return len(self.d)
 
@@ -238,6 +312,10 @@ class _NativeHostBackend:
     def address_scan_batch(self, queries):
         """``address_scan`` for each (addr, tag_mask, stake_sel): the owner map answers each directly."""
         return [self.address_scan(a, m, s) for a, m, s in queries]
+
+    def owner_totals(self, top, by_mask, log2_groups=0, tag_bits=32):
+        """Every owner's record and the whole-set info, grouped on the host (``owner_totals_of``)."""
+        return owner_totals_of(*self.records_payload())
 
     def __len__(self):
         return len(self.t)
@@ -384,6 +462,20 @@ class _GpuBackend:
         order = np.argsort(qidx, kind='stable')
         cuts = np.searchsorted(qidx[order], np.arange(n + 1))
         return [(recs[order[cuts[k]:cuts[k + 1]]], pay[order[cuts[k]:cuts[k + 1]]]) for k in range(n)]
+
+    def owner_totals(self, top, by_mask, log2_groups=0, tag_bits=32):
+        """Holders report from ONE pass over the HBM table (``utxo_owner_totals``: a hash aggregation by owner
+        key into a scratch group table, then a compaction; with ``top`` below the owner count a radix sort of
+        the metrics and a threshold compaction, which hands back every boundary tie). The group table has the
+        smallest power of two >= 2 x the booked live count slots, at least 16: distinct owners cannot exceed
+        the live entries, so it never fills on a consistent index."""
+        if not log2_groups:
+            log2_groups = min(31, (max(16, 2 * self.count) - 1).bit_length())
+        raw, owners, outputs, skipped, totals = self.L.utxo_owner_totals(
+            self.h, -1 if top is None else int(top), by_mask, log2_groups, tag_bits)
+        info = {'owners': int(owners), 'outputs': int(outputs), 'skipped': int(skipped),
+                'totals': np.asarray(totals, dtype=np.uint64)}
+        return np.frombuffer(raw, dtype=OWNER_DTYPE), info
 
     def records_payload(self):
         raw, pay = self.L.utxo_dump_payload(self.h)
@@ -624,6 +716,21 @@ class UtxoIndex:
             recs, pay = np.ascontiguousarray(recs[order]), np.ascontiguousarray(pay[order])
             out.append((recs, pay, int(pay['amount'].sum()) if len(pay) else 0))
         return out
+
+    @_locked
+    def owner_totals(self, top: Optional[int] = None, by: Sequence[int] = (0, 7), *, log2_groups: int = 0,
+                     tag_bits: int = 32):
+        """Holders report: ``(owners, info)`` over the whole index. An owner is a public key, so the 33-byte
+        and the 64-byte form of an address are one owner (OWNER_DTYPE / OWNER_COLUMNS above). ``top=None``:
+        every owner, ascending by key; ``top=N``: at most N owners in (metric descending, key ascending)
+        order, the metric being the sum of the ``by`` columns modulo 2^64. ``info`` is always over the whole
+        set: ``owners`` distinct owners, ``outputs`` entries grouped, ``skipped`` live entries without a
+        33/64-byte payload or with a tag above 6, ``totals`` u64[8]. GPU backend: one pass over the HBM table
+        (``_GpuBackend.owner_totals``); the keyword arguments size and weaken its scratch group table (test
+        levers, ignored by the host backends)."""
+        mask = _by_mask(top, by)
+        owners, info = self.be.owner_totals(top, mask, log2_groups, tag_bits)
+        return _owners_in_order(owners, top, mask), info
 
     @_locked
     def records_payload(self, sort: bool = True):

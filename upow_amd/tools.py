@@ -8,6 +8,13 @@ block order (reference: create_unspent_outputs.py:9-45, database.py:846-862).
 ``python -m upow_amd.tools address-utxos ADDRESS [ADDRESS ...]``: each address's live outputs in all seven output
 tables, one JSON line per address, straight from the UTXO index (on a GPU node ONE ``utxo_address_scan_batch``
 pass over the HBM table for all of them, K14).
+``python -m upow_amd.tools holders [--top N] [--by COL[,COL...]] [--db PATH] [--out FILE]``: who holds what. One
+JSON line per public key (both address forms folded): its spendable balance, stake and governance outputs, from
+one pass over the UTXO index (on a GPU node a hash aggregation over the HBM table, ``utxo_owner_totals``); every
+holder ascending by key, or with ``--top N`` the N greatest by the sum of the ``--by`` columns (default
+``spendable,stake``). The holder lines go to ``--out FILE`` when given; the last line printed is the summary
+``{"holders", "outputs", "skipped", "totals", "backend"}`` over the whole set. Exit status 1 when entries were
+skipped (indexed without their payload, so nobody can be credited with them).
 ``python -m upow_amd.tools materialise --db <rankN ledger>``: bring a lean cluster follower's SQL tables to its
 tip from its op log (ledger/lean.py); every other command does this first when the ledger has an op log.
 ``python -m upow_amd.tools sign-batch --keys F --digests F --out F [--device gpu|cpu]``: bulk RFC 6979 signing
@@ -85,6 +92,17 @@ async def address_utxos_many(addresses, path: str = None, db: Database = None) -
     return out
 
 
+async def holders(top: int = None, by=('spendable', 'stake'), path: str = None, db: Database = None):
+    """The ``holders`` command's lines: (one dict per holder in order, the summary dict), amounts as strings
+    (``Database.get_owner_totals``)."""
+    db = db or await open_ledger(path)
+    rows, summary = await db.get_owner_totals(top, tuple(by))
+    lines = [{**r, 'spendable': str(r['spendable']), 'stake': str(r['stake']),
+              'tables': {t: str(v) for t, v in r['tables'].items()}} for r in rows]
+    return lines, {**summary, 'totals': {c: str(v) for c, v in summary['totals'].items()},
+                   'backend': db.utxo.backend_name}
+
+
 async def rebuild_utxo(path: str = None):
     db = await open_ledger(path)
     outputs = await db.get_unspent_outputs_from_all_transactions()
@@ -128,13 +146,15 @@ def sign_batch(keys_path: str, digests_path: str, out_path: str, device: str = N
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('command', choices=['rebuild-utxo', 'utxo-hash', 'snapshot', 'verify-utxo', 'address-utxos',
-                                        'materialise', 'sign-batch'])
+                                        'holders', 'materialise', 'sign-batch'])
     ap.add_argument('address', nargs='*')
     ap.add_argument('--db', default=None)
     ap.add_argument('--out', default=None)
     ap.add_argument('--keys', default=None)
     ap.add_argument('--digests', default=None)
     ap.add_argument('--device', choices=['gpu', 'cpu'], default=None)
+    ap.add_argument('--top', type=int, default=None)
+    ap.add_argument('--by', default='spendable,stake')
     a = ap.parse_args(argv)
     if a.command == 'sign-batch':
         if not (a.keys and a.digests and a.out):
@@ -147,6 +167,22 @@ def main(argv=None):
             ap.error('address-utxos needs an ADDRESS')
         for res in asyncio.run(address_utxos_many(a.address, a.db)):  # one JSON line per address
             print(json.dumps(res))
+    elif a.command == 'holders':
+        if a.top is not None and a.top < 0:
+            ap.error('--top is a count >= 0')
+        try:
+            lines, summary = asyncio.run(holders(a.top, [c for c in a.by.split(',') if c], a.db))
+        except ValueError as e:
+            ap.error(str(e))
+        out = open(a.out, 'w') if a.out else sys.stdout
+        try:
+            for line in lines:  # one JSON line per holder
+                print(json.dumps(line), file=out)
+        finally:
+            if a.out:
+                out.close()
+        print(json.dumps(summary))
+        return 1 if summary['skipped'] else 0
     elif a.command == 'rebuild-utxo':
         asyncio.run(rebuild_utxo(a.db))
     elif a.command in ('snapshot', 'verify-utxo'):
