@@ -95,7 +95,7 @@ void p256_sign_gpu(const uint8_t* keys_be, const uint8_t* digests, int64_t n, ui
 void p256_candidates_host(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
 void p256_candidates_gpu(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
 
-// ---------------------------------------------------------------- HBM UTXO index (K7/K8/K9)
+// ---------------------------------------------------------------- HBM UTXO index (K7/K8/K9): utxo_table.hip
 // key records: 40 bytes {txid[32] raw, uint32 index, uint32 tag}
 int64_t utxo_create(uint32_t log2_cap);
 void utxo_destroy(int64_t h);
@@ -113,7 +113,13 @@ bool utxo_apply_async(int64_t h, const std::vector<UtxoSeg>& ins, bool with_pay,
                       uint32_t prev[3]);
 bool utxo_apply_wait(int64_t h, uint32_t out[3]);  // collect the pending async apply's counters
 std::vector<uint8_t> utxo_dump(int64_t h, std::vector<uint8_t>* payload_out);
-// K14: live outputs whose payload address equals addr[0:len] and whose tag is in tag_mask
+// test hooks (not called by the node): the table's home slot at capacity 2^log2_cap and K10's fingerprint of
+// each of n key records, from the kernels' own hash functions; the table's raw 48-byte slots (cap x 48 bytes)
+void utxo_debug_hashes(const uint8_t* recs, int64_t n, uint32_t log2_cap, uint32_t* home_out, uint64_t* fp_out);
+std::vector<uint8_t> utxo_debug_slots(int64_t h);
+
+// ---------------------------------------------------------------- K14 address scan: utxo_scan.hip
+// live outputs whose payload address equals addr[0:len] and whose tag is in tag_mask (a batch of one)
 std::vector<uint8_t> utxo_address_scan(int64_t h, const uint8_t* addr, uint32_t len, uint32_t tag_mask,
                                        uint32_t stake_sel, std::vector<uint8_t>& payload_out, uint64_t* total_out);
 // K14 for n queries in one table pass (ceil(n / 1024) launches under one lock hold): query i is addrs[64 i ..
@@ -128,7 +134,9 @@ struct AddressBatchOut {
 };
 void utxo_address_scan_batch(int64_t h, const uint8_t* addrs, const uint32_t* lens, const uint32_t* tag_masks,
                              const uint32_t* stake_sels, int64_t n, AddressBatchOut& out);
-// Holders report: every owner's totals in one table pass (a hash aggregation by canonical 33-byte owner key,
+
+// ---------------------------------------------------------------- holders report: utxo_owners.hip
+// Every owner's totals in one table pass (a hash aggregation by canonical 33-byte owner key,
 // the 33- and 64-byte forms of a key folded). `recs` are 112-byte records {key[33], pad[7], u32 outputs, u32
 // outputs in the 64-byte form, u64 sums[8]} in no particular order: every owner when top is -1, none when it
 // is 0, else every owner whose metric (sum of the by_mask columns mod 2^64) is at least the top-th greatest,
@@ -144,6 +152,7 @@ struct OwnerTotalsOut {
 void utxo_owner_totals(int64_t h, int64_t top, uint32_t by_mask, uint32_t log2_groups, uint32_t tag_bits,
                        OwnerTotalsOut& out);
 
+// ---------------------------------------------------------------- block input pass, K12 set hash: utxo_block.hip
 // whole-block input pass: lookup (K7) + duplicate candidates (K10) + per-tx fees (K11) in one round trip
 // Outputs of the whole-block input pass, written in place (the caller's arrays: no intermediate copies)
 struct BlockInputsOut {
@@ -163,10 +172,6 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
 std::vector<uint8_t> utxo_set_message(int64_t h, uint32_t tag, uint64_t* count_out);
 int64_t utxo_k12_snapshot(int64_t h, uint32_t tag);
 std::vector<uint8_t> utxo_k12_digest(int64_t id, uint64_t* count_out);
-// test hooks (not called by the node): the table's home slot at capacity 2^log2_cap and K10's fingerprint of
-// each of n key records, from the kernels' own hash functions; the table's raw 48-byte slots (cap x 48 bytes)
-void utxo_debug_hashes(const uint8_t* recs, int64_t n, uint32_t log2_cap, uint32_t* home_out, uint64_t* fp_out);
-std::vector<uint8_t> utxo_debug_slots(int64_t h);
 
 // ---------------------------------------------------------------- base58
 std::string b58encode(const uint8_t* data, size_t n);  // n <= kB58MaxInput

@@ -1,5 +1,5 @@
 // The UTXO index on the host (UPOW_UTXO_BACKEND=host, and every node without a GPU): the same record-level
-// contract as the HBM table of csrc/utxo_table.hip — 40-byte key records {txid, u32 index, u32 tag}, 80-byte
+// contract as the HBM table of csrc/utxo_table.hip (layouts: csrc/utxo_dev.h) — 40-byte key records {txid, u32 index, u32 tag}, 80-byte
 // payloads {u64 amount, u32 addr_len, u32 flags, addr[64]}, tags 0xff = absent / any — as a C++ hash map
 // with an owner-address index for K14, so a CPU node (the test suite, a gloo cluster rehearsal) applies a
 // block's index writes in one native call instead of a Python dict walk per outpoint.

@@ -1,5 +1,5 @@
 """Host-side cost of one 2 MB block's UTXO pass (K7 lookup + K10 duplicates + K11 fees in one round trip,
-csrc/utxo_table.hip utxo_block_inputs) on the HBM table, outside the ledger.
+csrc/utxo_block.hip utxo_block_inputs) on the HBM table, outside the ledger.
 
     python scripts/utxo_pass_bench.py [--inputs 16600] [--txs 8300] [--live 1000000] [--reps 300]
 

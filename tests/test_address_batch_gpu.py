@@ -42,14 +42,20 @@ def _colliders(fp):
     return [base, o_b0, o_b5, o_b32, o_long, o_long2]
 
 
-def _fill(tables, owners, n, seed, stake_rate=0.0):
-    """n outputs spread over ``owners`` in tables 0, 3 and 5, the same in every table of ``tables``."""
+def _rows(owners, n, seed, stake_rate=0.0):
+    """n outputs spread over ``owners`` in tables 0, 3 and 5: the key, owner, tag, amount and stake flag of each."""
     rng = random.Random(seed)
     keys = _keys(n, seed)
     own = [owners[k % len(owners)] for k in range(n)]  # every owner gets entries
     tags = [rng.choice(ALL_TAGS) for _ in keys]
     amounts = [rng.randrange(1, 1 << 44) for _ in keys]
     stake = [t == 0 and rng.random() < stake_rate for t in tags]
+    return keys, own, tags, amounts, stake
+
+
+def _fill(tables, owners, n, seed, stake_rate=0.0):
+    """The outputs of ``_rows``, the same in every table of ``tables``."""
+    keys, own, tags, amounts, stake = _rows(owners, n, seed, stake_rate)
     for t in ALL_TAGS:
         sel = [k for k in range(n) if tags[k] == t]
         pay = make_payload([amounts[k] for k in sel], [own[k] for k in sel], [stake[k] for k in sel])
@@ -220,3 +226,68 @@ def test_binding_totals_and_arguments(gpu):
     lens[2] = 65
     with pytest.raises(ValueError):
         gpu.utxo_address_scan_batch(g.be.h, addrs, lens, masks, sels)
+
+
+def _single_owners():
+    """Owners in the table and queries that must find nothing, at the edges where a batch of one could differ
+    from a scan with the query in kernel arguments."""
+    cs = _colliders(0x5eed1234)
+    o64 = _addr(0x22222222, 11, length=64, first=7)
+    # a 33-byte and two 64-byte owners, two more with the first one's fingerprint, and the fingerprints 0 and
+    # 0xffffffff: the ends of the one-entry fingerprint table
+    present = [cs[0], cs[1], cs[4], o64, _addr(0, 21), _addr(0xffffffff, 22)]
+    present += [_addr(0x01000000 + k, k) for k in range(3)]
+    # three absent owners with a present fingerprint, the 33-byte prefix of a present 64-byte owner, two ghosts
+    absent = [cs[2], cs[3], cs[5], o64[:33], _addr(1, 99), _addr(0xfffffffe, 98)]
+    return present, absent
+
+
+def _expected(rows, addr, tags, sel):
+    """(matches, amount sum) of one query, from the inserted rows themselves."""
+    _, own, tg, amounts, stake = rows
+    hit = [a for o, t, a, s in zip(own, tg, amounts, stake)
+           if o == addr and t in tags and (sel == STAKE_ANY or s == (sel == STAKE_ONLY))]
+    return len(hit), sum(hit)
+
+
+def _pairs(raw, pay):
+    """The (record, payload) pairs of a raw scan result, in an order of their own (the scan's is the atomics')."""
+    return sorted((raw[40 * k:40 * k + 40], pay[80 * k:80 * k + 80]) for k in range(len(raw) // 40))
+
+
+@pytest.mark.parametrize('log2_cap,n', [(8, 120), (12, 1900), (13, 4200)])
+def test_single_is_batch_of_one(gpu, log2_cap, n):
+    """``utxo_address_scan`` is ``utxo_address_scan_batch`` with one query: every case against the host table and
+    the sums of the inserted rows. At 2^13 slots one owner holds all 4200 outputs, so the scan takes the resize
+    pass (more than the first pass's 4096-record buffer)."""
+    g, h = _pair(log2_cap)
+    present, absent = _single_owners()
+    if n > 4096:
+        present, absent = present[:1], absent[:1]
+    rows = _rows(present, n, 59, stake_rate=0.4)
+    _fill((g, h), present, n, 59, stake_rate=0.4)
+    if n > 4096:
+        assert _expected(rows, present[0], ALL_TAGS, STAKE_ANY)[0] == n
+    nowhere = (1, 2, 4, 6)  # tables that hold no owner
+    for addr in present + absent:
+        for tags in (ALL_TAGS, (0,), nowhere):
+            for sel in (STAKE_ANY, STAKE_EXCLUDE, STAKE_ONLY):
+                want = _expected(rows, addr, tags, sel)
+                a, b = g.address_outputs(addr, tags, sel), h.address_outputs(addr, tags, sel)
+                assert (len(b[0]), b[2]) == want  # the host table on its own gives what the rows say
+                assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() and a[2] == b[2]
+                raw, pay, total = gpu.utxo_address_scan(g.be.h, addr, sum(1 << t for t in tags), sel)
+                amounts = np.frombuffer(pay, dtype=PAYLOAD_DTYPE)['amount']
+                assert (len(raw), len(amounts), total, int(amounts.sum())) == (40 * want[0], want[0], want[1], want[1])
+                if addr in absent or tags == nowhere:
+                    assert raw == b'' and pay == b'' and total == 0
+    assert all(_expected(rows, present[0], (0,), sel)[0] > 0 for sel in (STAKE_EXCLUDE, STAKE_ONLY))
+    # bytes past the stated length are no part of the query: the bytes form cannot carry any, a batch row can
+    row = np.full((1, 64), 0xee, dtype=np.uint8)
+    row[0, :33] = np.frombuffer(present[0], dtype=np.uint8)
+    one = np.ones(1, dtype=np.uint32)
+    qidx, raw_b, pay_b, totals = gpu.utxo_address_scan_batch(g.be.h, row, 33 * one, 0b101001 * one, 0 * one)
+    raw, pay, total = gpu.utxo_address_scan(g.be.h, present[0], 0b101001)
+    assert len(raw) > 0 and _pairs(raw_b, pay_b) == _pairs(raw, pay) and int(totals[0]) == total and not qidx.any()
+    with pytest.raises(ValueError):
+        gpu.utxo_address_scan(g.be.h, bytes(65), 1)

@@ -33,7 +33,7 @@ def both(g, h, case, top=None, by=(0, 7), extra_skipped=0, **levers):
 
 
 def owner_home(key33, log2_groups):
-    """The group-table slot the pass starts at for an owner key: ``owner_hash`` of csrc/utxo_table.hip."""
+    """The group-table slot the pass starts at for an owner key: ``owner_hash`` of csrc/utxo_owners.hip."""
     w = [int.from_bytes(key33[1 + 4 * i:5 + 4 * i], 'little') for i in range(8)]
     h = (0x9E3779B97F4A7C15 * (key33[0] + 1)) & M64
     for i in range(4):

@@ -183,7 +183,7 @@ def test_address_outputs_host(backend):
 
 @pytest.mark.gpu
 def test_address_outputs_gpu_scan(gpu):
-    """K14 utxo_address_scan kernel vs a plain host filter; the device amount sum matches too, and a
+    """K14 utxo_address_scan (csrc/utxo_scan.hip: a batch of one) vs a plain host filter; the device amount sum matches too, and a
     result larger than the first-pass output buffer (4096) takes the resize pass."""
     idx = UtxoIndex(backend='gpu')
     owners, want = _address_case(idx, 21)

@@ -18,14 +18,14 @@ from upow_amd.ledger.utxo import (MISSING, PAYLOAD_DTYPE, STAKE_EXCLUDE, STAKE_O
 HOSTS = ['host', 'host-py']
 BACKENDS = [*HOSTS, pytest.param('gpu', marks=pytest.mark.gpu)]
 EMPTY, FULL, TOMB = 0, 1, 2
-# csrc/utxo_table.hip UtxoSlot: key words, meta (state | index << 8 | tag << 16), owner fingerprint, padding
+# csrc/utxo_dev.h UtxoSlot: key words, meta (state | index << 8 | tag << 16), owner fingerprint, padding
 SLOT_DTYPE = np.dtype([('k', '<u4', (8,)), ('meta', '<u4'), ('fp', '<u4'), ('pad', '<u4', (2,))])
 assert SLOT_DTYPE.itemsize == 48
 M64 = (1 << 64) - 1
 
 
 # ---------------------------------------------------------------------------------------------------------
-# mirrors of the device hashes (csrc/utxo_table.hip slot_hash, outpoint_fp) over packed 40-byte records
+# mirrors of the device hashes (csrc/utxo_dev.h slot_hash, outpoint_fp) over packed 40-byte records
 
 def _words(recs):
     return np.ascontiguousarray(recs[:, :32]).view('<u4').reshape(len(recs), 8)

@@ -327,7 +327,7 @@ async def _create_block_fast(block_content: str, d: dict, error_list: list, last
     roctx.push('block:utxo_pass')
 
     # ---- inputs: one device pass = lookup (existence in unspent_outputs + amount + address),
-    #      duplicate detection and per-tx fees (csrc/utxo_table.hip utxo_block_inputs)
+    #      duplicate detection and per-tx fees (csrc/utxo_block.hip utxo_block_inputs)
     in_keys = np.frombuffer(d['in_keys'], dtype=np.uint8).reshape(-1, 40)
     n_in = len(in_keys)
     in_start, out_start = _i32(d, 'in_start'), _i32(d, 'out_start')

@@ -32,7 +32,7 @@ TAG_BY_TABLE = {
 TABLE_BY_TAG = {v: k for k, v in TAG_BY_TABLE.items()}
 MISSING = 0xFF
 
-# per-outpoint payload carried by the index (csrc/utxo_table.hip UtxoPayload): the spent output's
+# per-outpoint payload carried by the index (csrc/utxo_dev.h UtxoPayload): the spent output's
 # amount in smallest units, flags (bit 0: unspent_outputs.is_stake = 1) and its raw address bytes
 # (33 compressed / 64 uncompressed)
 PAYLOAD_DTYPE = np.dtype([('amount', '<u8'), ('len', '<u4'), ('flags', '<u4'), ('addr', 'u1', (64,))])
@@ -688,8 +688,9 @@ class UtxoIndex:
     def address_outputs(self, addr: bytes, tags: Iterable[int] = (0,), stake_sel: int = STAKE_ANY):
         """K14 (reference ``database.py:909-937,1138-1205``): the live outpoints whose payload address is
         ``addr`` (raw 33/64 bytes, prefix normalised as stored) in the given tables, as (records, payloads)
-        in canonical (txid, index) order, plus their amount sum in smallest units. GPU backend: one
-        ``utxo_address_scan`` launch over the HBM table instead of an index walk."""
+        in canonical (txid, index) order, plus their amount sum in smallest units. GPU backend: one pass
+        over the HBM table instead of an index walk (``utxo_address_scan``: a batch of one query through the
+        batch kernel of csrc/utxo_scan.hip)."""
         mask = 0
         for t in tags:
             mask |= 1 << int(t)
@@ -703,7 +704,7 @@ class UtxoIndex:
         """:meth:`address_outputs` for each ``(addr, tags, stake_sel)`` of ``queries``: one
         ``(records, payloads, amount_sum)`` per query, in query order, each what the single call returns.
         GPU backend: every query is answered by the same pass over the HBM table
-        (``utxo_address_scan_batch``), where single calls make one pass each."""
+        (``utxo_address_scan_batch``), where single calls, each a batch of one, make one pass each."""
         qs = []
         for addr, tags, stake_sel in queries:
             mask = 0
@@ -760,7 +761,7 @@ class UtxoIndex:
     def block_inputs(self, in_keys: np.ndarray, in_start: np.ndarray, out_amount: np.ndarray,
                      out_start: np.ndarray, want_tag: int = 0):
         """One pass over a block's inputs: K7 lookup (tag + payload), K10 duplicate detection and K11
-        per-tx fees. GPU backend: one H2D/D2H round trip and three kernels (csrc/utxo_table.hip).
+        per-tx fees. GPU backend: one H2D/D2H round trip and three kernels (csrc/utxo_block.hip).
 
         Returns (tags u8[n_in], payload[n_in], dup_of u32[n_in] (1 + earlier duplicate, else 0),
         fee i64[n_tx], missing u32[n_tx], n_dup)."""
