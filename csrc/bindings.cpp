@@ -397,6 +397,24 @@ PYBIND11_MODULE(_native, m) {
        "The first `count` RFC 6979 HMAC_DRBG candidates (32 bytes big-endian each) for key and digest, accepted "
        "or not, from the batched signer's shared core: the only way to exercise the DRBG's retry update.");
 
+    m.def("p256_probe", [](const std::string& op, py::buffer a, py::buffer b, const std::string& mode) -> py::bytes {
+        py::buffer_info ba = a.request(), bb = b.request();
+        const auto* pa = static_cast<const uint8_t*>(ba.ptr);
+        const auto* pb = static_cast<const uint8_t*>(bb.ptr);
+        const size_t na = size_t(ba.size * ba.itemsize), nb = size_t(bb.size * bb.itemsize);
+        std::vector<uint8_t> o;
+        {
+            py::gil_scoped_release rel;
+            o = p256_probe(op, pa, na, pb, nb, mode);
+        }
+        return py::bytes(reinterpret_cast<const char*>(o.data()), o.size());
+    }, py::arg("op"), py::arg("a"), py::arg("b") = py::bytes(), py::arg("mode") = "host",
+       "FOR TESTS ONLY: operation `op` of the P-256 kernels' field, scalar and point arithmetic (csrc/p256_probe.h) "
+       "over flat little-endian operands a and b, one item per host iteration (mode 'host') or GPU lane ('ilp': "
+       "built like the block-latency kernels, 'occ': like the batch kernel). 'quad_' / 'oct_' + mul4, sqr4, dbl4, "
+       "add4 run a lane group and, on the GPU, return every lane's copy. ValueError for an unknown op or mode or "
+       "operands that are not whole items.");
+
     auto recs_arg = [](py::buffer b, int64_t& n) {
         py::buffer_info bi = b.request();
         const int64_t nb = bi.size * bi.itemsize;

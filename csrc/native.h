@@ -94,6 +94,15 @@ void p256_sign_gpu(const uint8_t* keys_be, const uint8_t* digests, int64_t n, ui
 // core on one host thread / one GPU thread. They leak the nonce.
 void p256_candidates_host(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
 void p256_candidates_gpu(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
+// test hook (not called by the node; csrc/p256_probe.h): operation `op` of the kernels' field, scalar and point
+// arithmetic on n items of flat little-endian 32-bit words, operands a (and b, empty for one-operand operations).
+// mode 'host': a host loop; 'ilp': a kernel of p256.hip (ILP-first scheduler); 'occ': a kernel of p256_batch.hip
+// (default scheduler). The lane-group operations ('quad_' / 'oct_' + mul4, sqr4, dbl4, add4; host and ilp only)
+// return one copy of the result per lane of each group on the device (4 or 8), one per group on the host.
+// std::invalid_argument for an unknown op or mode, or operand lengths that are not n whole items.
+std::vector<uint8_t> p256_probe(const std::string& op, const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes,
+                                const std::string& mode);
+void p256_probe_occ_launch(int op, const uint32_t* a, const uint32_t* b, uint8_t* out, int64_t n, void* stream);
 
 // ---------------------------------------------------------------- HBM UTXO index (K7/K8/K9): utxo_table.hip
 // key records: 40 bytes {txid[32] raw, uint32 index, uint32 tag}

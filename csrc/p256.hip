@@ -35,6 +35,7 @@
 #include "thread_pool.h"
 #include "streams.h"
 #include "p256_field.h"
+#include "p256_probe.h"
 #include "p256_verify.h"
 #include "sha256_common.h"
 
@@ -164,9 +165,6 @@ static uint8_t verify_one_host(const VerifyItem& it, const aff* gtab) {
 // The schedule is written once over a policy type: QuadDev broadcasts through DPP on the GPU;
 // QuadHost (one host thread) computes every product of a step itself, which lets the CPU tests check
 // the formulas and the step schedule bit for bit against the reference verifier.
-struct xz { fe x, y, zz, zzz; };  // XYZZ point; zz == 0 <=> infinity
-static_assert(sizeof(xz) == 128, "xz layout");
-
 struct QuadHost {
     UPOW_HD void sqr4(const fe& a0, const fe& a1, const fe& a2, const fe& a3, fe& r0, fe& r1, fe& r2, fe& r3) const {
         const fe m0 = fe_sqr(a0), m1 = fe_sqr(a1), m2 = fe_sqr(a2), m3 = fe_sqr(a3);
@@ -184,9 +182,6 @@ struct QuadHost {
         r3 = m3;
     }
 };
-
-// the eight-lane kernel's pair-split product (OctDev below) on one host thread: both lanes' halves
-UPOW_HD fe mul_pair_host(const fe& a, const fe& b);
 
 struct OctHost {
     UPOW_HD void sqr4(const fe& a0, const fe& a1, const fe& a2, const fe& a3, fe& r0, fe& r1, fe& r2, fe& r3) const {
@@ -256,47 +251,9 @@ struct QuadDev {
 // crosses to its partner with DPP row_shl:4, the lower lane adds it and reduces, and row_shr:4 hands the
 // reduced product back to the upper lane; quad_perm broadcasts then give all four products to every lane
 // of both quads. 8,300 signatures fill 1,038 waves, one per SIMD of the chip, where the quad kernel left
-// half of the SIMDs idle. `split_rows` / `combine_rows` are the arithmetic; the host test runs them on one
-// thread (both halves) against fe_mul.
-UPOW_HD void split_rows(uint32_t p[12], const fe& a, const fe& b, bool upper) {
-    uint32_t ar[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ar[i] = upper ? a.v[4 + i] : a.v[i];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) p[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned cy = 0;
-        uint32_t prev = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint64_t t = uint64_t(ar[i]) * b.v[j] + p[i + j];
-            p[i + j] = __builtin_addc(uint32_t(t), prev, cy, &cy);
-            prev = uint32_t(t >> 32);
-        }
-        p[i + 8] = prev + cy;
-    }
-}
-// lo: columns 0..11 of the lower rows; hi: columns 4..15 of the upper rows (hi[w] is column w + 4)
-UPOW_HD fe combine_rows(const uint32_t lo[12], const uint32_t hi[12]) {
-    uint32_t c[16];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) c[w] = lo[w];
-    unsigned cy = 0;
-#pragma unroll
-    for (int w = 4; w < 12; ++w) c[w] = __builtin_addc(lo[w], hi[w - 4], cy, &cy);
-#pragma unroll
-    for (int w = 12; w < 16; ++w) c[w] = __builtin_addc(0u, hi[w - 4], cy, &cy);
-    return fe_reduce(c);
-}
-
-UPOW_HD fe mul_pair_host(const fe& a, const fe& b) {
-    uint32_t lo[12], hi[12];
-    split_rows(lo, a, b, false);
-    split_rows(hi, a, b, true);
-    return combine_rows(lo, hi);
-}
-
+// half of the SIMDs idle. `split_rows` / `combine_rows` (csrc/p256_verify.h) are the arithmetic;
+// tests/test_p256_arith.py runs them on one thread (mul_pair_host: both halves) against a*b mod p, and
+// tests/test_p256_arith_gpu.py checks what every lane of an octet receives from mul_pair and the broadcasts.
 struct OctDev {
     bool is1, is2, is3, hi;  // lane & 3, and whether the lane is in the octet's upper quad
     __device__ __forceinline__ fe pick(const fe& a0, const fe& a1, const fe& a2, const fe& a3) const {
@@ -445,12 +402,6 @@ UPOW_HD jac mul_g16_quarter(const fe& k, const aff* tab16, int quarter) {
         if (b) acc = jac_madd(acc, t[size_t(j) * kG16Ent + b]);
     }
     return acc;
-}
-
-// Jacobian (X, Y, Z) -> XYZZ (X, Y, Z^2, Z^3): the same affine point, one lane on its own
-UPOW_HD xz jac_to_xz(const jac& p) {
-    const fe zz = fe_sqr(p.z);
-    return xz{p.x, p.y, zz, fe_mul(zz, p.z)};
 }
 
 // Shared verify body. `tab` holds this signature's 16 window entries 1Q..16Q (global scratch on the GPU, a
@@ -925,6 +876,132 @@ void p256_decompress_gpu(const uint8_t* in, int64_t n, uint8_t* out, uint8_t* ok
     io.d2h(out, d_out, 64 * size_t(n));
     io.d2h(ok, d_ok, size_t(n));
     io.finish("decompress");
+}
+
+// ------------------------------------------------------------------------------------------------
+// arithmetic probe (test hook, csrc/p256_probe.h; never called by the node)
+// ------------------------------------------------------------------------------------------------
+// One item per lane, built with this file's ILP-first scheduler (`ilp`; p256_batch.hip has the `occ` twin).
+template <int OP>
+__global__ __launch_bounds__(256) void p256_probe_ilp_kernel(const uint32_t* __restrict__ a,
+                                                              const uint32_t* __restrict__ b, uint8_t* __restrict__ out,
+                                                              int64_t n, int a_words, int b_words, int out_bytes) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    probe::one<OP>(a + i * a_words, b + i * b_words, out + i * out_bytes);
+}
+
+// One group per lane quad in the geometry of p256_verify_quad_kernel (16 groups per wave, four waves per
+// workgroup, a group at or past n returns as a whole). Every lane stores all it holds after the operation, as
+// copy (lane & 3) of its group: 128 bytes, the four products of mul4 / sqr4 or the point of dbl4 / add4.
+template <int OP>
+__global__ __launch_bounds__(256, 1) void p256_probe_quad_kernel(const uint32_t* __restrict__ a,
+                                                                  const uint32_t* __restrict__ b,
+                                                                  uint8_t* __restrict__ out, int64_t n, int a_words,
+                                                                  int b_words) {
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t g = (int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6)) * 16 + (lane >> 2);
+    if (g >= n) return;
+    const int role = lane & 3;
+    const QuadDev pp{(role & 1) != 0, (role & 2) != 0};
+    probe::group<OP>(pp, a + g * a_words, b + g * b_words, out + (g * 4 + role) * 128);
+}
+
+// The same per lane octet, in the geometry of p256_verify_oct_kernel (8 groups per wave): copy (lane & 7).
+template <int OP>
+__global__ __launch_bounds__(256, 1) void p256_probe_oct_kernel(const uint32_t* __restrict__ a,
+                                                                 const uint32_t* __restrict__ b,
+                                                                 uint8_t* __restrict__ out, int64_t n, int a_words,
+                                                                 int b_words) {
+    const int lane = int(threadIdx.x) & 63;
+    const int64_t g = (int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6)) * 8 + (lane >> 3);
+    if (g >= n) return;
+    const int role = lane & 3;
+    const bool upper = (lane & 4) != 0;
+    const OctDev pp{role == 1, role == 2, role == 3, upper};
+    probe::group<OP>(pp, a + g * a_words, b + g * b_words, out + (g * 8 + (lane & 7)) * 128);
+}
+
+std::vector<uint8_t> p256_probe(const std::string& op_name, const uint8_t* a, size_t a_bytes, const uint8_t* b,
+                                size_t b_bytes, const std::string& mode) {
+    // 'quad_' / 'oct_' select the step policy of a lane-group operation
+    int lanes = 1;
+    std::string base = op_name;
+    if (base.rfind("quad_", 0) == 0) { lanes = 4; base = base.substr(5); }
+    else if (base.rfind("oct_", 0) == 0) { lanes = 8; base = base.substr(4); }
+    int op = -1;
+    for (int k = 0; k < probe::kOps; ++k)
+        if (base == probe::shape(k).name) op = k;
+    if (op < 0 || (lanes == 1) != (op < probe::kOneLaneOps)) throw std::invalid_argument("p256_probe: unknown op " + op_name);
+    const bool host = mode == "host", ilp = mode == "ilp", occ = mode == "occ";
+    if (!host && !ilp && !occ) throw std::invalid_argument("p256_probe: unknown mode " + mode);
+    if (occ && lanes != 1) throw std::invalid_argument("p256_probe: the lane-group operations have modes host and ilp");
+    if (!host && lanes == 1 && op >= probe::kOneLaneDeviceOps)
+        throw std::invalid_argument("p256_probe: " + op_name + " has mode host only");
+    const probe::Shape sh = probe::shape(op);
+    const size_t ia = 4 * size_t(sh.a_words), ib = 4 * size_t(sh.b_words);
+    if (a_bytes % ia) throw std::invalid_argument("p256_probe: operand a is not a whole number of items");
+    const int64_t n = int64_t(a_bytes / ia);
+    if (b_bytes != size_t(n) * ib) throw std::invalid_argument("p256_probe: operand b does not match operand a");
+    const size_t copies = host ? 1 : size_t(lanes);
+    std::vector<uint8_t> out(size_t(n) * copies * size_t(sh.out_bytes));
+    if (n == 0) return out;
+    if (host) {
+        std::vector<uint32_t> wa(a_bytes / 4), wb(b_bytes / 4 + 1);
+        std::memcpy(wa.data(), a, a_bytes);
+        if (b_bytes) std::memcpy(wb.data(), b, b_bytes);
+        auto loop = [&](auto&& item) {
+            for (int64_t i = 0; i < n; ++i)
+                item(wa.data() + i * sh.a_words, wb.data() + i * sh.b_words, out.data() + i * sh.out_bytes);
+        };
+        if (lanes == 1)
+            probe::dispatch_one(op, [&](auto K) {
+                loop([](const uint32_t* x, const uint32_t* y, uint8_t* o) { probe::one<decltype(K)::value>(x, y, o); });
+            });
+        else if (lanes == 4)
+            probe::dispatch_group(op, [&](auto K) {
+                loop([](const uint32_t* x, const uint32_t* y, uint8_t* o) { probe::group<decltype(K)::value>(QuadHost{}, x, y, o); });
+            });
+        else
+            probe::dispatch_group(op, [&](auto K) {
+                loop([](const uint32_t* x, const uint32_t* y, uint8_t* o) { probe::group<decltype(K)::value>(OctHost{}, x, y, o); });
+            });
+        return out;
+    }
+    node_device_enter();
+    PooledBuf<uint32_t> b_a{a_bytes / 4}, b_b{b_bytes / 4};
+    PooledBuf<uint8_t> b_out{out.size()};
+    StagedIO io(a_bytes + b_bytes + out.size());
+    io.h2d(b_a.p, a, a_bytes);
+    io.h2d(b_b.p, b, b_bytes);
+    hipStream_t st = node_stream();
+    if (occ) {
+        p256_probe_occ_launch(op, b_a.p, b_b.p, b_out.p, n, st);
+    } else if (lanes == 1) {
+        probe::dispatch_one(op, [&](auto K) {
+            constexpr int k = decltype(K)::value;
+            if constexpr (k < probe::kOneLaneDeviceOps)
+                hipLaunchKernelGGL(p256_probe_ilp_kernel<k>, dim3(unsigned((n + 255) / 256)), dim3(256), 0, st, b_a.p, b_b.p,
+                                   b_out.p, n, sh.a_words, sh.b_words, sh.out_bytes);
+        });
+        hck(hipGetLastError(), "p256_probe_ilp_kernel launch");
+    } else {
+        const int64_t waves = lanes == 4 ? (n + 15) / 16 : (n + 7) / 8;
+        const dim3 grid(unsigned((waves + 3) / 4));
+        probe::dispatch_group(op, [&](auto K) {
+            constexpr int k = decltype(K)::value;
+            if (lanes == 4)
+                hipLaunchKernelGGL(p256_probe_quad_kernel<k>, grid, dim3(256), 0, st, b_a.p, b_b.p, b_out.p, n, sh.a_words,
+                                   sh.b_words);
+            else
+                hipLaunchKernelGGL(p256_probe_oct_kernel<k>, grid, dim3(256), 0, st, b_a.p, b_b.p, b_out.p, n, sh.a_words,
+                                   sh.b_words);
+        });
+        hck(hipGetLastError(), "p256_probe lane-group kernel launch");
+    }
+    io.d2h(out.data(), b_out.p, out.size());
+    io.finish("p256 probe");
+    return out;
 }
 
 bool p256_pubkey(const uint8_t d_be[32], uint8_t out_le[64]) {

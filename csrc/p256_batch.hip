@@ -14,6 +14,7 @@
 #include <string>
 
 #include "native.h"
+#include "p256_probe.h"
 #include "p256_verify.h"
 
 namespace upow {
@@ -112,6 +113,30 @@ void p256_batch_launch(char variant, const void* items, int64_t n, const void* g
                            status, spw);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) throw std::runtime_error(std::string("p256_verify_kernel launch: ") + hipGetErrorString(e));
+}
+
+// Test hook (csrc/p256_probe.h): one item of a one-lane operation per lane, built with this file's default
+// scheduler (`occ`; the same text under the ILP-first schedule is p256_probe_ilp_kernel in csrc/p256.hip).
+template <int OP>
+__global__ __launch_bounds__(256) void p256_probe_occ_kernel(const uint32_t* __restrict__ a,
+                                                              const uint32_t* __restrict__ b, uint8_t* __restrict__ out,
+                                                              int64_t n, int a_words, int b_words, int out_bytes) {
+    const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    probe::one<OP>(a + i * a_words, b + i * b_words, out + i * out_bytes);
+}
+
+void p256_probe_occ_launch(int op, const uint32_t* a, const uint32_t* b, uint8_t* out, int64_t n, void* stream) {
+    if (op < 0 || op >= probe::kOneLaneDeviceOps) throw std::invalid_argument("p256_probe: not a one-lane device operation");
+    const probe::Shape sh = probe::shape(op);
+    probe::dispatch_one(op, [&](auto K) {
+        constexpr int k = decltype(K)::value;
+        if constexpr (k < probe::kOneLaneDeviceOps)
+            hipLaunchKernelGGL(p256_probe_occ_kernel<k>, dim3(unsigned((n + 255) / 256)), dim3(256), 0,
+                               static_cast<hipStream_t>(stream), a, b, out, n, sh.a_words, sh.b_words, sh.out_bytes);
+    });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) throw std::runtime_error(std::string("p256_probe_occ_kernel launch: ") + hipGetErrorString(e));
 }
 
 }  // namespace upow

@@ -167,8 +167,12 @@ UPOW_HD void sqr_512(uint32_t c[16], const fe& a) {
 // NIST fast reduction of a 512-bit value mod p (FIPS 186-4 D.2.3):
 //   c mod p = s1 + 2 s2 + 2 s3 + s4 + s5 - s6 - s7 - s8 - s9 (mod p)
 // evaluated with 32-bit add/sub-with-carry chains (v_add_co/v_addc on gfx950; int64 limbs cost
-// 64-bit shift-adds plus sign-extension moves), then the signed overflow T in [-4, 6] is folded with
+// 64-bit shift-adds plus sign-extension moves), then the signed overflow T is folded with
 // 2^256 == K = 2^224 - 2^192 - 2^96 + 1 (mod p) and the result brought into [0, p) branch-free.
+// T = floor(sum / 2^256) lies in [-4, 4]: the sum is linear in each word of c, so its extremes have every word
+// at 0 or 0xffffffff by the sign of that word's coefficient, and those two inputs give -4 and 4
+// (tests/p256_operands.py solinas_extreme; the positive rows alone would allow 6, but they share words with
+// the negative ones).
 #define UPOW_ACC(OP, S)                                                     \
     {                                                                       \
         unsigned cy_ = 0;                                                   \

@@ -110,4 +110,59 @@ UPOW_HD jac mul_g16(const fe& k, const aff* tab16) {
     }
     return acc;
 }
+
+// XYZZ coordinates (x = X/ZZ, y = Y/ZZZ) of the lane-group kernels (csrc/p256.hip)
+struct xz { fe x, y, zz, zzz; };  // XYZZ point; zz == 0 <=> infinity
+static_assert(sizeof(xz) == 128, "xz layout");
+
+// Jacobian (X, Y, Z) -> XYZZ (X, Y, Z^2, Z^3): the same affine point, one lane on its own
+UPOW_HD xz jac_to_xz(const jac& p) {
+    const fe zz = fe_sqr(p.z);
+    return xz{p.x, p.y, zz, fe_mul(zz, p.z)};
+}
+
+// The arithmetic of the eight-lane kernel's pair-split product (csrc/p256.hip OctDev::mul_pair): each lane of a
+// pair (k, k + 4) runs four of the eight schoolbook rows (`split_rows`), the lower lane adds the upper lane's
+// 12-word partial sum to its own and reduces (`combine_rows`). mul_pair_host plays both lanes on one thread;
+// tests/test_p256_arith.py (check_field_binary, operation 'mul_pair' of the p256_probe hook) compares it with
+// a*b mod p on the operand pairs fe_mul gets, among them the ones whose column-11 carry runs through columns
+// 12..15, and tests/test_p256_arith_gpu.py runs the same pairs through both device builds.
+UPOW_HD void split_rows(uint32_t p[12], const fe& a, const fe& b, bool upper) {
+    uint32_t ar[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ar[i] = upper ? a.v[4 + i] : a.v[i];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) p[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        unsigned cy = 0;
+        uint32_t prev = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint64_t t = uint64_t(ar[i]) * b.v[j] + p[i + j];
+            p[i + j] = __builtin_addc(uint32_t(t), prev, cy, &cy);
+            prev = uint32_t(t >> 32);
+        }
+        p[i + 8] = prev + cy;
+    }
+}
+// lo: columns 0..11 of the lower rows; hi: columns 4..15 of the upper rows (hi[w] is column w + 4)
+UPOW_HD fe combine_rows(const uint32_t lo[12], const uint32_t hi[12]) {
+    uint32_t c[16];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) c[w] = lo[w];
+    unsigned cy = 0;
+#pragma unroll
+    for (int w = 4; w < 12; ++w) c[w] = __builtin_addc(lo[w], hi[w - 4], cy, &cy);
+#pragma unroll
+    for (int w = 12; w < 16; ++w) c[w] = __builtin_addc(0u, hi[w - 4], cy, &cy);
+    return fe_reduce(c);
+}
+
+UPOW_HD fe mul_pair_host(const fe& a, const fe& b) {
+    uint32_t lo[12], hi[12];
+    split_rows(lo, a, b, false);
+    split_rows(hi, a, b, true);
+    return combine_rows(lo, hi);
+}
 }  // namespace upow

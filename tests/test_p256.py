@@ -9,6 +9,8 @@ import pytest
 from upow_amd.ops import p256 as op
 from upow_amd.utils import p256 as o
 
+from p256_operands import legacy_field_cases, legacy_scalar_cases
+
 RFC6979_D = 0xC9AFA9D845BA75166B5C215767B1D6934E50C3DB36E89B127B8A622B120F6721
 
 
@@ -35,19 +37,16 @@ def test_native_sign_pubkey_match_oracle(native):
 def test_scalar_inverse_divsteps_matches_pow(native):
     """s^-1 * 2^256 mod n by the verifier's divsteps inverse (p256_field.h sc_inv_safegcd_mont) against
     Python's pow, on random scalars and on the shapes that stress a gcd: small values, powers of two, n - k,
-    values just below 2^256 reduced, and runs of ones."""
+    values just below 2^256 reduced, and runs of ones (the list is p256_operands.legacy_scalar_cases, which
+    test_p256_arith.py extends and also runs on the device)."""
     from upow_amd.ops.native import lib
     inv = lib().p256_scalar_inv_mont
     n = o.N
     R = (1 << 256) % n
-    rng = random.Random(11)
-    cases = [1, 2, 3, n - 1, n - 2, (n - 1) // 2, (1 << 255) % n, (1 << 256) - 1 - n, (1 << 128) - 1]
-    cases += [1 << k for k in range(256)] + [n - (1 << k) for k in range(255)]
-    cases += [((1 << k) - 1) % n for k in range(1, 257)] + [rng.randrange(1, n) for _ in range(3000)]
+    cases = legacy_scalar_cases()
+    assert len(cases) >= 3770
     for s in cases:
-        s %= n
-        if s == 0:
-            continue
+        assert 0 < s < n
         got = int.from_bytes(inv(s.to_bytes(32, 'little')), 'little')
         assert got == pow(s, -1, n) * R % n, hex(s)
 
@@ -55,23 +54,18 @@ def test_scalar_inverse_divsteps_matches_pow(native):
 def test_field_arithmetic_matches_python(native):
     """The kernels' field code (p256_field.h, run on the host): products, squares, sums and differences
     mod p against Python integers, and the Solinas reduction of arbitrary 512-bit values — including the
-    words patterns that drive its signed overflow to both ends of [-4, 6] (the h = -1 and h = 1 folds)."""
+    words patterns that drive its signed overflow to both ends of [-4, 4] (the h = -1 and h = 1 folds). The
+    cases are p256_operands.legacy_field_cases, drawn as this test always drew them."""
     from upow_amd.ops.native import lib
     L = lib()
     p = o.P
-    rng = random.Random(13)
-    edge = [0, 1, 2, p - 1, p - 2, (p - 1) // 2, 1 << 255, (1 << 224) - 1, (1 << 96) + 5, p - (1 << 96),
-            (1 << 256) - 1 - (1 << 224) - p // 3]
-    vals = [v % p for v in edge] + [rng.randrange(p) for _ in range(1500)]
-    vals += [sum(rng.choice((0, 0xffffffff, 1)) << (32 * k) for k in range(8)) % p for _ in range(500)]
-    for k in range(len(vals)):
-        a, b = vals[k], vals[rng.randrange(len(vals))]
+    pairs, wide = legacy_field_cases()
+    assert len(pairs) == 2011 and len(wide) == 4000
+    for a, b in pairs:
         out = L.p256_fe_ops(a.to_bytes(32, 'little'), b.to_bytes(32, 'little'))
         got = [int.from_bytes(out[32 * i:32 * i + 32], 'little') for i in range(4)]
         assert got == [a * b % p, a * a % p, (a + b) % p, (a - b) % p], (hex(a), hex(b))
-    words = (0, 1, 0xffffffff, 0x80000000, 0xfffffffe)
-    for _ in range(4000):
-        c = sum(rng.choice(words) << (32 * k) for k in range(16)) if rng.random() < 0.7 else rng.getrandbits(512)
+    for c in wide:
         assert int.from_bytes(L.p256_fe_reduce(c.to_bytes(64, 'little')), 'little') == c % p, hex(c)
 
 
