@@ -397,6 +397,45 @@ PYBIND11_MODULE(_native, m) {
        "The first `count` RFC 6979 HMAC_DRBG candidates (32 bytes big-endian each) for key and digest, accepted "
        "or not, from the batched signer's shared core: the only way to exercise the DRBG's retry update.");
 
+    // K16 vanity search (csrc/p256_vanity.h, not constant-time): see native.h for the contract
+    m.def("p256_vanity_info", []() {
+        const VanityInfo i = p256_vanity_info();
+        py::dict d;
+        d["keys_per_lane"] = i.keys_per_lane;
+        d["lanes_per_block"] = i.lanes_per_block;
+        d["keys_per_launch"] = i.keys_per_launch;
+        d["max_ranges"] = i.max_ranges;
+        return d;
+    });
+    m.def("p256_vanity_search", [](py::bytes base_be, int64_t count, py::bytes ranges, int64_t max_hits, bool gpu,
+                                   int threads, int64_t launch_keys, int64_t launch_lanes) -> py::tuple {
+        const std::string b = base_be, r = ranges;
+        if (b.size() != 32) throw std::invalid_argument("base must be 32 bytes big-endian");
+        if (r.size() % 66) throw std::invalid_argument("ranges must be R x 66 bytes (lo | hi, 33 bytes big-endian each)");
+        VanityHits h;
+        {
+            py::gil_scoped_release rel;
+            h = p256_vanity_search(reinterpret_cast<const uint8_t*>(b.data()), count,
+                                   reinterpret_cast<const uint8_t*>(r.data()), int64_t(r.size() / 66), max_hits, gpu,
+                                   threads, launch_keys, launch_lanes);
+        }
+        return py::make_tuple(h.total, py::bytes(reinterpret_cast<const char*>(h.indexes.data()), 8 * h.indexes.size()));
+    }, py::arg("base_be"), py::arg("count"), py::arg("ranges"), py::arg("max_hits"), py::arg("gpu"),
+       py::arg("threads") = 8, py::arg("launch_keys") = 0, py::arg("launch_lanes") = 0);
+    m.def("p256_vanity_walk", [](py::bytes base_be, int64_t count, bool gpu, int threads, int64_t launch_keys,
+                                 int64_t launch_lanes) -> py::bytes {
+        const std::string b = base_be;
+        if (b.size() != 32) throw std::invalid_argument("base must be 32 bytes big-endian");
+        std::vector<uint8_t> o;
+        {
+            py::gil_scoped_release rel;
+            o = p256_vanity_walk(reinterpret_cast<const uint8_t*>(b.data()), count, gpu, threads, launch_keys, launch_lanes);
+        }
+        return py::bytes(reinterpret_cast<const char*>(o.data()), o.size());
+    }, py::arg("base_be"), py::arg("count"), py::arg("gpu"), py::arg("threads") = 8, py::arg("launch_keys") = 0,
+       py::arg("launch_lanes") = 0,
+       "FOR TESTS: the 33 address bytes of the keys base .. base + count - 1 from the vanity search's core.");
+
     m.def("p256_probe", [](const std::string& op, py::buffer a, py::buffer b, const std::string& mode) -> py::bytes {
         py::buffer_info ba = a.request(), bb = b.request();
         const auto* pa = static_cast<const uint8_t*>(ba.ptr);

@@ -8,7 +8,8 @@
 // and copy goes to the device's node stream (csrc/streams.h) and each call synchronises that stream
 // before its buffers are released: a later call's H2D copy into a recycled buffer is ordered after
 // the earlier kernels that used it. Memory is never returned to the driver; the high-water mark is
-// bounded by the largest batch (a few tens of MB per device).
+// bounded by the largest batch (a few tens of MB per device for the node's calls). A process that runs the
+// vanity search (csrc/p256_vanity.hip) also keeps that search's workspace, 128 MiB for a full launch.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -94,6 +94,28 @@ void p256_sign_gpu(const uint8_t* keys_be, const uint8_t* digests, int64_t n, ui
 // core on one host thread / one GPU thread. They leak the nonce.
 void p256_candidates_host(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
 void p256_candidates_gpu(const uint8_t key_be[32], const uint8_t digest[32], int count, uint8_t* out);
+// K16 vanity search (core: csrc/p256_vanity.h, not constant-time; csrc/p256_vanity.hip): the keys of the scalars
+// base + i, i in [0, count), walked with batched affine additions on the GPU or by the same core on the host
+// pool; needs 1 <= base and base + count <= n. `ranges66` are n_ranges x (lo | hi), 33 bytes big-endian each:
+// half-open, non-empty, sorted and disjoint ranges of the 33 address bytes read as a big-endian integer.
+// total = the number of i whose address lies in a range; indexes = those i ascending, any max_hits of them when
+// there are more. launch_keys / launch_lanes (0: the defaults of p256_vanity_info) shrink a GPU launch: test
+// levers. std::invalid_argument for arguments outside these rules; std::runtime_error if a batch inversion
+// met a zero factor (a defect: no keys are returned then). The device and pinned copies of base are overwritten.
+struct VanityInfo {
+    int keys_per_lane, lanes_per_block, max_ranges;  // keys per batch inversion; threads per block; ranges per call
+    int64_t keys_per_launch;
+};
+VanityInfo p256_vanity_info();
+struct VanityHits {
+    uint64_t total = 0;
+    std::vector<uint64_t> indexes;
+};
+VanityHits p256_vanity_search(const uint8_t base_be[32], int64_t count, const uint8_t* ranges66, int64_t n_ranges,
+                              int64_t max_hits, bool gpu, int threads, int64_t launch_keys, int64_t launch_lanes);
+// test hook: the 33 address bytes of every walked key, from the search's core with another sink (count <= 2^21)
+std::vector<uint8_t> p256_vanity_walk(const uint8_t base_be[32], int64_t count, bool gpu, int threads,
+                                      int64_t launch_keys, int64_t launch_lanes);
 // test hook (not called by the node; csrc/p256_probe.h): operation `op` of the kernels' field, scalar and point
 // arithmetic on n items of flat little-endian 32-bit words, operands a (and b, empty for one-operand operations).
 // mode 'host': a host loop; 'ilp': a kernel of p256.hip (ILP-first scheduler); 'occ': a kernel of p256_batch.hip

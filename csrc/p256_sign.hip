@@ -97,28 +97,6 @@ static void launch_check(const char* what) {
 // ------------------------------------------------------------------------------------------------
 // host entry points (GPU)
 // ------------------------------------------------------------------------------------------------
-// Overwrites the device and pinned copies of a call's secret bytes. device() queues the device memset on the
-// node stream (ahead of the call's final sync); the destructor clears the pinned bytes after that sync, and on
-// an error path does both itself. Declared after the PooledBuf it covers, so it runs before the buffer goes
-// back to the pool.
-struct SecretScrub {
-    uint8_t* dev;
-    uint8_t* pinned;
-    size_t n;
-    bool dev_done = false;
-    void device() {
-        node_memset(dev, 0, n, "scrub secrets");
-        dev_done = true;
-    }
-    ~SecretScrub() {
-        if (!dev_done) {
-            (void)hipMemsetAsync(dev, 0, n, node_stream());
-            (void)hipStreamSynchronize(node_stream());
-        }
-        std::memset(pinned, 0, n);
-    }
-};
-
 // Keys (| digests) in one H2D, one launch, x | y (r | s) and the ok flags adjacent on the device and back in
 // one D2H, all on the node stream. digests == nullptr: public keys.
 static void sign_or_pubkey_gpu(const uint8_t* keys_be, const uint8_t* digests, int64_t n, uint8_t* out, uint8_t* ok) {

@@ -99,6 +99,28 @@ inline void node_sync(const char* what = "node stream sync") {
     stream_check(hipStreamSynchronize(node_stream()), what);
 }
 
+// Overwrites the device and pinned copies of a call's secret bytes. device() queues the device memset on the
+// node stream (ahead of the call's final sync); the destructor clears the pinned bytes after that sync, and on
+// an error path does both itself. Declared after the PooledBuf it covers, so it runs before the buffer goes
+// back to the pool (csrc/p256_sign.hip, csrc/p256_vanity.hip).
+struct SecretScrub {
+    uint8_t* dev;
+    uint8_t* pinned;
+    size_t n;
+    bool dev_done = false;
+    void device() {
+        node_memset(dev, 0, n, "scrub secrets");
+        dev_done = true;
+    }
+    ~SecretScrub() {
+        if (!dev_done) {
+            (void)hipMemsetAsync(dev, 0, n, node_stream());
+            (void)hipStreamSynchronize(node_stream());
+        }
+        std::memset(pinned, 0, n);
+    }
+};
+
 // Pinned staging for one node-side call's transfers (per thread, grown on demand, never returned: the
 // HIP runtime may be gone when threads exit). A pageable hipMemcpyAsync is a staged, host-synchronous
 // copy, and every node_d2h above ends in its own stream sync; a block's UTXO pass made five of them. With

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -140,6 +141,56 @@ static void test_p256() {
     for (int threads : {1, 3, 8}) CHECK(p256_verify_host(items.data(), n, threads) == want);
 }
 
+// K16 on the host pool: a short walk and one search from base = 1 against p256_pubkey, key by key
+static void test_vanity_host() {
+    const VanityInfo info = p256_vanity_info();
+    const int64_t count = 70 * info.keys_per_lane + 3;  // 71 work items: enough for the pool to use its threads
+    uint8_t base[32] = {0};
+    base[31] = 1;
+    std::vector<std::vector<uint8_t>> want;
+    for (int64_t i = 0; i < count; ++i) {
+        uint8_t d[32] = {0}, q[64];
+        d[29] = uint8_t((1 + i) >> 16);
+        d[30] = uint8_t((1 + i) >> 8);
+        d[31] = uint8_t(1 + i);
+        CHECK(p256_pubkey(d, q));
+        std::vector<uint8_t> a(33);
+        a[0] = (q[32] & 1) ? 43 : 42;
+        std::memcpy(a.data() + 1, q, 32);
+        want.push_back(a);
+    }
+    for (int threads : {1, 4}) {
+        const std::vector<uint8_t> got = p256_vanity_walk(base, count, false, threads, 0, 0);
+        CHECK(int64_t(got.size()) == 33 * count);
+        for (int64_t i = 0; i < count && got.size() == size_t(33 * count); ++i)
+            CHECK(std::memcmp(got.data() + 33 * i, want[size_t(i)].data(), 33) == 0);
+    }
+    // the even-y half of the address space, and the one-value range of key 7 (33 bytes big-endian: the address itself)
+    uint8_t ranges[2 * 66] = {0};
+    ranges[0] = 42;
+    ranges[33] = 43;
+    std::vector<uint64_t> even;
+    for (int64_t i = 0; i < count; ++i)
+        if (want[size_t(i)][0] == 42) even.push_back(uint64_t(i));
+    VanityHits h = p256_vanity_search(base, count, ranges, 1, count, false, 4, 0, 0);
+    CHECK(h.total == even.size() && h.indexes == even);
+    h = p256_vanity_search(base, count, ranges, 1, 3, false, 4, 0, 0);  // more hits than the buffer takes
+    CHECK(h.total == even.size() && h.indexes.size() == 3);
+    std::memcpy(ranges, want[7].data(), 33);
+    std::memcpy(ranges + 33, want[7].data(), 33);
+    for (int k = 65; k >= 33 && ++ranges[k] == 0; --k) {}  // hi = lo + 1
+    h = p256_vanity_search(base, count, ranges, 1, 8, false, 1, 0, 0);
+    CHECK(h.total == 1 && h.indexes == std::vector<uint64_t>{7});
+    bool threw = false;
+    try {
+        uint8_t zero[32] = {0};
+        p256_vanity_walk(zero, 1, false, 1, 0, 0);
+    } catch (const std::invalid_argument&) {
+        threw = true;
+    }
+    CHECK(threw);
+}
+
 static void test_pow_host() {
     PowJobHost job;
     job.header.assign(108, 0);
@@ -157,6 +208,7 @@ int main() {
     test_sha256();
     test_base58();
     test_p256();
+    test_vanity_host();
     test_pow_host();
     if (failures) {
         std::fprintf(stderr, "%d failure(s)\n", failures);

@@ -3,7 +3,7 @@
 #
 #   tools/sanitize_host.sh [outdir]          (FUZZ_SECONDS=N per fuzz target, default 20)
 #
-# 1. tools/host_selftest.cpp + the host crypto (SHA-256, SHA-NI, base58, P-256) under ASan + UBSan;
+# 1. tools/host_selftest.cpp + the host crypto (SHA-256, SHA-NI, base58, P-256, the vanity walk's host path) under ASan + UBSan;
 #    the host worker pool (csrc/thread_pool.h) under ThreadSanitizer.
 # 2. libFuzzer + ASan + UBSan on the parsers of untrusted network input: the tx decoder every pushed tx and
 #    every peer block goes through (csrc/txdecode.h, tools/fuzz/fuzz_txdecode.cpp) and the HTTP/1.1 +
@@ -39,9 +39,9 @@ stale() {  # $1 = object, rest = inputs: rebuild when any input is newer
   for i in "$@"; do [ "$i" -nt "$o" ] && return 0; done
   return 1
 }
-HDRS="csrc/native.h csrc/sha256_common.h csrc/p256_field.h csrc/p256_verify.h"
+HDRS="csrc/native.h csrc/sha256_common.h csrc/p256_field.h csrc/p256_verify.h csrc/p256_sign.h csrc/p256_vanity.h"
 echo "== [1] host selftest (ASan + UBSan) and host pool (TSan)"
-for h in p256 p256_batch; do  # the verify TU and the one-lane batch kernel's TU it launches
+for h in p256 p256_batch p256_vanity; do  # the verify TU, the one-lane batch kernel's TU it launches, the vanity walk
   if stale "$OUT/$h.o" csrc/$h.hip $HDRS; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -Xarch_host -O0 -g1 -std=c++17 -I/opt/rocm/include $SAN_HOST \
       -c csrc/$h.hip -o "$OUT/$h.o"
@@ -53,7 +53,7 @@ for f in csrc/sha256_host.cpp csrc/sha256_ni.cpp csrc/base58.cpp csrc/p256_host.
     $CXX $CFLAGS -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -c "$f" -o "$o"
   fi
 done
-$CXX -fsanitize=address,undefined -pthread "$OUT"/host_selftest.o "$OUT"/p256.o "$OUT"/p256_batch.o "$OUT"/sha256_host.o \
+$CXX -fsanitize=address,undefined -pthread "$OUT"/host_selftest.o "$OUT"/p256.o "$OUT"/p256_batch.o "$OUT"/p256_vanity.o "$OUT"/sha256_host.o \
   "$OUT"/sha256_ni.o "$OUT"/base58.o "$OUT"/p256_host.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o "$OUT/host_selftest"
 # leak checking off: the HIP runtime keeps process-lifetime allocations
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 "$OUT/host_selftest"

@@ -1,4 +1,4 @@
-"""P-256 front end: single sign/verify (host C++) and batched verify/decompress/keygen/sign (gfx950 kernels).
+"""P-256 front end: single sign/verify (host C++) and batched verify/decompress/keygen/sign/vanity search (gfx950 kernels).
 
 Batch record layout (160 B, little-endian like the wire format): ``qx | qy | r | s | e`` where ``e``
 is the SHA-256 digest of the signed message (big-endian, as hashed). Status codes: 1 valid,
@@ -144,6 +144,38 @@ def sign_records(keys: Sequence[int], digests: Sequence[bytes], device: Optional
     return recs
 
 
+# ---------------------------------------------------------------------------------------------- vanity search
+def vanity_on_gpu(device: Optional[str] = None) -> bool:
+    """Where a vanity search runs, whatever its size: the GPU when there is one, unless ``device`` says otherwise
+    (``find`` sizes its calls by the same answer)."""
+    if device is None:
+        return gpu_available()
+    if device not in ('gpu', 'cpu'):
+        raise ValueError("device must be 'gpu', 'cpu' or None")
+    return device == 'gpu'
+
+
+def vanity_search(base: int, count: int, ranges: Sequence[Tuple[int, int]], max_hits: int = 4096,
+                  device: Optional[str] = None) -> Tuple[int, np.ndarray]:
+    """Which of the private keys ``base + i``, ``i`` in [0, count), have an address whose 33 bytes, read as a
+    big-endian integer, lie in one of ``ranges`` (half-open ``(lo, hi)``, sorted and disjoint: wallet/vanity.py
+    ``prefix_ranges``) -> ``(number of hits, their i ascending as uint64)``; any ``max_hits`` of them when there
+    are more, the number still exact. K16 (csrc/p256_vanity.h; not constant-time, ``base`` is a secret: bulk work
+    on a trusted machine) on the GPU or the same core on host threads (:func:`vanity_on_gpu`; ``device`` as in
+    :func:`public_keys`).
+    ``ValueError`` unless 1 <= base and base + count <= n, and for malformed ranges."""
+    if not 0 <= int(count) < 1 << 63:
+        raise ValueError('count must be in [0, 2**63)')
+    try:
+        base_be = int(base).to_bytes(32, 'big')
+        packed = b''.join(int(lo).to_bytes(33, 'big') + int(hi).to_bytes(33, 'big') for lo, hi in ranges)
+    except OverflowError:
+        raise ValueError('base or a range bound does not fit its field') from None
+    total, idx = lib().p256_vanity_search(base_be, int(count), packed, int(max_hits), vanity_on_gpu(device),
+                                          max(1, min(cpu_budget(), 16)))
+    return int(total), np.frombuffer(idx, dtype='<u8')
+
+
 # ---------------------------------------------------------------------------------------------- admission
 # reference: every /push_tx verifies its signatures one at a time on the node's event loop
 # (transaction_input.py:100-109 via fastecdsa). Inside an admission context (utils/coalesce.py) the
@@ -194,4 +226,4 @@ def decompress(addresses33: Sequence[bytes], device: Optional[str] = None):
 
 
 __all__ = ['public_key', 'sign', 'verify', 'verify_async', 'verify_records', 'decompress', 'record', 'EcdsaError', 'oracle',
-           'public_keys', 'sign_digests', 'sign_records', 'SIGN_GPU_MIN']
+           'public_keys', 'sign_digests', 'sign_records', 'SIGN_GPU_MIN', 'vanity_search', 'vanity_on_gpu']

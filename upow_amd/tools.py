@@ -21,6 +21,10 @@ tip from its op log (ledger/lean.py); every other command does this first when t
 (K15 batched, ops/p256.py sign_digests; not constant-time, for a machine the operator trusts). F are raw files:
 32-byte big-endian private keys, 32-byte SHA-256 digests, and 64-byte ``r | s`` little-endian out. One JSON
 line with counts and seconds; a key outside [1, n-1] gets 64 zero bytes and exit status 1.
+``python -m upow_amd.tools vanity PREFIX [--ignore-case] [--count K] [--max-keys N] [--out F] [--device gpu|cpu]``:
+K private keys whose addresses start with PREFIX (K16, wallet/vanity.py; not constant-time, for a machine the
+operator trusts), as JSON in the format of ``key_pair_list.json`` to F or standard output. The key store is not
+touched. Exit status 1 when a search gave up after ``--max-keys`` keys.
 """
 from __future__ import annotations
 
@@ -143,10 +147,24 @@ def sign_batch(keys_path: str, digests_path: str, out_path: str, device: str = N
             'seconds': round(seconds, 6)}
 
 
+def vanity_keys(prefix: str, ignore_case: bool = False, count: int = 1, max_keys: int = None, device: str = None) -> list:
+    """``count`` key pairs whose addresses start with ``prefix``, each from a fresh random base; fewer when a
+    search gave up after ``max_keys`` keys."""
+    from .wallet import vanity
+    keys = []
+    for _ in range(count):
+        found = vanity.find(prefix, ignore_case, device=device, max_keys=max_keys,
+                            progress=vanity.progress_printer())
+        if found is None:
+            break
+        keys.append({'private_key': found[0], 'public_key': found[1]})
+    return keys
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('command', choices=['rebuild-utxo', 'utxo-hash', 'snapshot', 'verify-utxo', 'address-utxos',
-                                        'holders', 'materialise', 'sign-batch'])
+                                        'holders', 'materialise', 'sign-batch', 'vanity'])
     ap.add_argument('address', nargs='*')
     ap.add_argument('--db', default=None)
     ap.add_argument('--out', default=None)
@@ -155,6 +173,9 @@ def main(argv=None):
     ap.add_argument('--device', choices=['gpu', 'cpu'], default=None)
     ap.add_argument('--top', type=int, default=None)
     ap.add_argument('--by', default='spendable,stake')
+    ap.add_argument('--ignore-case', action='store_true')
+    ap.add_argument('--count', type=int, default=1)
+    ap.add_argument('--max-keys', type=int, default=None)
     a = ap.parse_args(argv)
     if a.command == 'sign-batch':
         if not (a.keys and a.digests and a.out):
@@ -162,6 +183,22 @@ def main(argv=None):
         res = sign_batch(a.keys, a.digests, a.out, a.device)
         print(json.dumps(res))
         return 1 if res['failed'] else 0
+    elif a.command == 'vanity':
+        if len(a.address) != 1 or a.count < 1:
+            ap.error('vanity needs one PREFIX and --count >= 1')
+        from .wallet import vanity
+        try:
+            print(vanity.progress_line(a.address[0], a.ignore_case), file=sys.stderr)
+        except ValueError as e:
+            ap.error(str(e))
+        keys = vanity_keys(a.address[0], a.ignore_case, a.count, a.max_keys, a.device)
+        text = json.dumps({'keys': keys})
+        if a.out:
+            with open(a.out, 'w') as f:
+                f.write(text)
+        else:
+            print(text)
+        return 0 if len(keys) == a.count else 1
     elif a.command == 'address-utxos':
         if not a.address:
             ap.error('address-utxos needs an ADDRESS')

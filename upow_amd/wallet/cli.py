@@ -3,6 +3,9 @@
 ``python -m upow_amd.wallet {createwallet,send,balance,stake,unstake,register_inode,de_register_inode,
 register_validator,vote,revoke} [-to R] [-a AMOUNT] [-m MSG] [-r RANGE] [-from ADDR]``
 
+``createwallet --prefix P [--ignore-case] [--max-keys N]`` searches for a key whose address starts with P
+(wallet/vanity.py: on the GPU when there is one) and stores it like a random one.
+
 Keys live in ``<data dir>/key_pair_list.json`` ({"keys": [{"private_key", "public_key"}]}); the wallet
 reads the local ledger directly and pushes through the node's ``/push_tx`` (falling back to a direct
 mempool insert, like the reference). The reference's single-key ``select_key`` bug (reads
@@ -78,14 +81,29 @@ async def main(argv=None):
     ap.add_argument('-r', dest='range', required=False)
     ap.add_argument('-from', dest='revoke_from', required=False)
     ap.add_argument('-k', dest='key_index', type=int, required=False, help='key index (skips the prompt)')
+    ap.add_argument('--prefix', default=None, help='createwallet: search for an address that starts with this')
+    ap.add_argument('--ignore-case', action='store_true', help='--prefix matches in any mix of cases')
+    ap.add_argument('--max-keys', type=int, default=None, help='--prefix: give up after this many keys')
     args = ap.parse_args(argv)
     store = key_store()
     database = await Database.get()
     cmd = args.command
     if cmd == 'createwallet':
         key_list = store.get('keys') or []
-        d = op.oracle.gen_private_key()
-        address = point_to_string(op.public_key(d))
+        if args.prefix is not None:
+            from . import vanity
+            try:
+                print(vanity.progress_line(args.prefix, args.ignore_case))
+            except ValueError as e:
+                ap.error(str(e))
+            found = vanity.find(args.prefix, args.ignore_case, max_keys=args.max_keys, progress=vanity.progress_printer())
+            if found is None:
+                print(f'No address with prefix {args.prefix!r} in {args.max_keys} keys')
+                return
+            d, address = found
+        else:
+            d = op.oracle.gen_private_key()
+            address = point_to_string(op.public_key(d))
         key_list.append({'private_key': d, 'public_key': address})
         store.set('keys', key_list)
         print(f'Private key: {hex(d)}\nAddress: {address}')
