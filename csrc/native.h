@@ -45,13 +45,10 @@ std::vector<uint8_t> sha256_batch_gpu(const uint8_t* data, int64_t nbytes, const
 std::vector<uint8_t> p256_verify_host(const uint8_t* items, int64_t n, int threads);
 // one 160-byte VerifyItem on 64-bit limbs (csrc/p256_host.cpp); status as p256_verify_host
 uint8_t p256_verify_one_host64(const uint8_t* item);
-// p256.hip's fixed-base table: 32 x 256 affine points, each x[8] y[8] little-endian u32 words
+// p256_tables.hip's fixed-base table: 32 x 256 affine points, each x[8] y[8] little-endian u32 words
 const void* p256_g_table_host();
 // s^-1 * 2^256 mod n for s in [1, n) (little-endian 64-bit limbs): the divsteps inverse of p256_field.h
 void p256_scalar_inv_mont_host(uint64_t out[4], const uint64_t s[4]);
-// a*b, a^2, a+b, a-b mod p (8 little-endian 32-bit limbs each, canonical inputs); c (16 limbs) mod p
-void p256_fe_ops_host(const uint32_t a[8], const uint32_t b[8], uint32_t out[32]);
-void p256_fe_reduce_host(const uint32_t c[16], uint32_t out[8]);
 // the cluster's per-block commit vote on a native RCCL communicator of its own (csrc/rccl_vote.hip)
 // one-lane-per-signature batch verify launch (csrc/p256_batch.hip): VerifyItem items, 16-bit G table,
 // 16 window-table entries of scratch per signature, status bytes
@@ -68,6 +65,7 @@ std::vector<uint8_t> p256_g16_entries(int64_t first, int64_t count);
 // that table on the current device (a device pointer to 16 x 65,536 x {x[8], y[8]}), built on first use
 const void* p256_g16_table_device();
 std::vector<uint8_t> p256_verify_gpu(const uint8_t* items, int64_t n);
+// decompression of 33-byte addresses (csrc/p256_keys.hip, as the on-curve check below)
 void p256_decompress_host(const uint8_t* in33, int64_t n, uint8_t* out64, uint8_t* ok);
 void p256_decompress_gpu(const uint8_t* in33, int64_t n, uint8_t* out64, uint8_t* ok);
 // signer keys decompressed into verify items on the device, output addresses curve-checked, signatures
@@ -118,7 +116,7 @@ std::vector<uint8_t> p256_vanity_walk(const uint8_t base_be[32], int64_t count, 
                                       int64_t launch_keys, int64_t launch_lanes);
 // test hook (not called by the node; csrc/p256_probe.h): operation `op` of the kernels' field, scalar and point
 // arithmetic on n items of flat little-endian 32-bit words, operands a (and b, empty for one-operand operations).
-// mode 'host': a host loop; 'ilp': a kernel of p256.hip (ILP-first scheduler); 'occ': a kernel of p256_batch.hip
+// mode 'host': a host loop; 'ilp': a kernel of p256_probe.hip (ILP-first scheduler); 'occ': a kernel of p256_batch.hip
 // (default scheduler). The lane-group operations ('quad_' / 'oct_' + mul4, sqr4, dbl4, add4; host and ilp only)
 // return one copy of the result per lane of each group on the device (4 or 8), one per group on the host.
 // std::invalid_argument for an unknown op or mode, or operand lengths that are not n whole items.

@@ -1,7 +1,8 @@
 // K5 batch path: one lane per signature for batches past kQuadMaxBatch (csrc/p256.hip), where the chip is
 // full either way and one lane per signature does a quarter of the quad kernel's redundant work.
 //
-// This file is compiled with the default (occupancy-first) machine scheduler, unlike p256.hip: the
+// This file is compiled with the default (occupancy-first) machine scheduler, unlike p256.hip (the ILP-first
+// files are listed in upow_amd/_build.py DEVICE_FLAGS): the
 // default variant runs four waves per SIMD at 128 VGPRs, where the ILP-first schedule that shortens the
 // block-latency kernels' dependency chains spills 85 VGPRs instead of 52. The throughput is the same under
 // both schedules (19.05 vs 19.11 M sig/s at 132,800 in one session, profiles/r5/p256batch).
@@ -16,6 +17,7 @@
 #include "native.h"
 #include "p256_probe.h"
 #include "p256_verify.h"
+#include "streams.h"
 
 namespace upow {
 
@@ -111,12 +113,11 @@ void p256_batch_launch(char variant, const void* items, int64_t n, const void* g
     else
         hipLaunchKernelGGL((p256_verify_kernel<4, false>), dim3(grid), dim3(block), 0, stream_, d_items, n, d_tab, d_scratch,
                            status, spw);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw std::runtime_error(std::string("p256_verify_kernel launch: ") + hipGetErrorString(e));
+    launch_check("p256_verify_kernel");
 }
 
 // Test hook (csrc/p256_probe.h): one item of a one-lane operation per lane, built with this file's default
-// scheduler (`occ`; the same text under the ILP-first schedule is p256_probe_ilp_kernel in csrc/p256.hip).
+// scheduler (`occ`; the same text under the ILP-first schedule is p256_probe_ilp_kernel in csrc/p256_probe.hip).
 template <int OP>
 __global__ __launch_bounds__(256) void p256_probe_occ_kernel(const uint32_t* __restrict__ a,
                                                               const uint32_t* __restrict__ b, uint8_t* __restrict__ out,
@@ -135,8 +136,7 @@ void p256_probe_occ_launch(int op, const uint32_t* a, const uint32_t* b, uint8_t
             hipLaunchKernelGGL(p256_probe_occ_kernel<k>, dim3(unsigned((n + 255) / 256)), dim3(256), 0,
                                static_cast<hipStream_t>(stream), a, b, out, n, sh.a_words, sh.b_words, sh.out_bytes);
     });
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw std::runtime_error(std::string("p256_probe_occ_kernel launch: ") + hipGetErrorString(e));
+    launch_check("p256_probe_occ_kernel");
 }
 
 }  // namespace upow

@@ -9,7 +9,7 @@
 // -> 128-bit schoolbook, so this file has its own:
 //  * Montgomery multiplication (CIOS, R = 2^256) for both the field prime p and the group order n, with
 //    the constants (R mod m, R^2 mod m, -m^-1 mod 2^64) derived at start-up, not typed in;
-//  * u1*G from the fixed-base byte-window table of p256.hip (32 mixed additions), converted once into
+//  * u1*G from the fixed-base byte-window table of p256_tables.hip (32 mixed additions), converted once into
 //    the Montgomery domain;
 //  * u2*Q with a 4-bit fixed window (252 doublings + <= 64 additions), a = -3 doubling formula;
 //  * no inversion in the field: x(R) == r is checked as X == r*Z^2 (and (r+n)*Z^2 when r+n < p).
@@ -130,7 +130,7 @@ struct Aff { Fe x, y; };
 struct Ctx {
     Mod p, n;
     Fe b_m, three_m;
-    std::vector<Aff> g;  // [32][256] Montgomery-form copy of p256.hip's fixed-base table
+    std::vector<Aff> g;  // [32][256] Montgomery-form copy of p256_tables.hip's fixed-base table
 };
 
 inline void to_mont(Fe& r, const uint64_t a[4], const Mod& M) { mont_mul(r.v, a, M.rr, M); }

@@ -5,9 +5,10 @@
 //
 // Every operation reads its operands from flat arrays of little-endian 32-bit words (an fe is 8 words, a jac
 // x | y | z, an aff x | y, an xz x | y | zz | zzz) and writes its result to a flat array. Items share no state and
-// there is no barrier. The text is instantiated three times: a host loop (csrc/p256.hip, `host`), a kernel in
-// csrc/p256.hip under that file's ILP-first scheduler (`ilp`, next to QuadDev and OctDev) and a kernel in
-// csrc/p256_batch.hip under the default scheduler (`occ`). Each operation calls the existing function unchanged.
+// there is no barrier. The text is instantiated three times: a host loop (csrc/p256_probe.hip, `host`), a kernel
+// in csrc/p256_probe.hip under the ILP-first scheduler the verify TU csrc/p256.hip is built with (`ilp`) and a
+// kernel in csrc/p256_batch.hip under the default scheduler (`occ`). Each operation calls the existing function
+// unchanged; the lane-group operations and their step policies are csrc/p256_steps.h.
 //
 // The probe checks what the arithmetic computes under each file's device flags. It cannot show that the copy
 // inlined into a production kernel is the same machine code; the whole-signature tests stay for that.
@@ -19,6 +20,7 @@
 
 #include "p256_field.h"
 #include "p256_sign.h"
+#include "p256_steps.h"
 #include "p256_verify.h"
 
 namespace upow {

@@ -6,7 +6,7 @@
 // The text below is UPOW_HD and templated on the SHA-256 compression (`Compress`: st[8], w[16] -> st, w may
 // be clobbered) and on the fixed-base multiplication (`MulG`: scalar -> k*G in Jacobian form), so the kernels
 // of csrc/p256_sign.hip (dev_compress, the 16-bit window table in HBM) and a host thread (host_compress_words,
-// the byte-window table) run the same code. csrc/p256.hip's p256_sign / p256_pubkey are written separately
+// the byte-window table) run the same code. csrc/p256_sign.hip's p256_sign / p256_pubkey are written separately
 // (byte-oriented HMAC, Fermat inverse) and stay the reference this code is tested against.
 //
 // NOT CONSTANT TIME: the fixed-base multiplication skips zero windows of the secret scalar, the table reads
@@ -156,7 +156,7 @@ UPOW_HD bool pubkey_one(const MulG& mulg, const fe& d, aff& q) {
 }
 
 // ECDSA over the digest (as the integer bits2int(digest), not yet reduced) with the RFC 6979 nonce; the steps
-// of p256_sign (csrc/p256.hip). false: key outside [1, n - 1], or no usable candidate in kSignMaxCandidates.
+// of p256_sign (csrc/p256_sign.hip). false: key outside [1, n - 1], or no usable candidate in kSignMaxCandidates.
 template <class Compress, class MulG>
 UPOW_HD bool sign_one(const Compress& c, const MulG& mulg, const fe& d, const fe& digest, fe& r, fe& s) {
     if (!sign_key_ok(d)) return false;

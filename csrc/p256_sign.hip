@@ -89,11 +89,6 @@ __global__ __launch_bounds__(64) void p256_candidates_kernel(const uint8_t* __re
     }
 }
 
-static void launch_check(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + " launch: " + hipGetErrorString(e));
-}
-
 // ------------------------------------------------------------------------------------------------
 // host entry points (GPU)
 // ------------------------------------------------------------------------------------------------
@@ -190,6 +185,95 @@ void p256_candidates_host(const uint8_t key_be[32], const uint8_t digest[32], in
     Rfc6979<HostCompress> drbg;
     drbg.init(HostCompress{}, fe_from_be(key_be), sc_reduce(fe_from_be(digest)));
     for (int j = 0; j < count; ++j) fe_to_be(drbg.next(HostCompress{}), out + 32 * j);
+}
+
+// ------------------------------------------------------------------------------------------------
+// single-signature host reference (wallets): written separately from sign_one, byte-wise, so the tests can
+// compare the two
+// ------------------------------------------------------------------------------------------------
+bool p256_pubkey(const uint8_t d_be[32], uint8_t out_le[64]) {
+    const fe d = fe_from_be(d_be);
+    if (fe_is_zero(d) || fe_geq(d, fe_const_n())) return false;
+    aff a;
+    if (!jac_to_aff(mul_g(d, static_cast<const aff*>(p256_g_table_host())), a)) return false;
+    fe_to_le(a.x, out_le);
+    fe_to_le(a.y, out_le + 32);
+    return true;
+}
+
+// HMAC-SHA256
+static void hmac_sha256(const uint8_t* key, size_t klen, const uint8_t* msg, size_t mlen, uint8_t out[32]) {
+    uint8_t k0[64] = {0};
+    if (klen > 64) host_sha256(key, klen, k0); else std::memcpy(k0, key, klen);
+    uint8_t ipad[64], opad[64];
+    for (int i = 0; i < 64; ++i) { ipad[i] = k0[i] ^ 0x36; opad[i] = k0[i] ^ 0x5c; }
+    HostSha256 h1;
+    h1.update(ipad, 64);
+    h1.update(msg, mlen);
+    uint8_t inner[32];
+    h1.final(inner);
+    HostSha256 h2;
+    h2.update(opad, 64);
+    h2.update(inner, 32);
+    h2.final(out);
+}
+
+// RFC 6979 (HMAC-SHA256, qlen = 256) + ECDSA sign over a SHA-256 digest. Returns r,s little-endian.
+bool p256_sign(const uint8_t d_be[32], const uint8_t digest[32], uint8_t r_le[32], uint8_t s_le[32]) {
+    const fe d = fe_from_be(d_be);
+    const fe n = fe_const_n();
+    if (fe_is_zero(d) || fe_geq(d, n)) return false;
+    const fe e = sc_reduce(fe_from_be(digest));
+    uint8_t h1[32];
+    fe_to_be(e, h1);  // bits2octets(h1) = int2octets(bits2int(h1) mod q)
+    uint8_t V[32], K[32];
+    std::memset(V, 0x01, 32);
+    std::memset(K, 0x00, 32);
+    uint8_t buf[32 + 1 + 32 + 32];
+    auto step = [&](uint8_t sep) {
+        std::memcpy(buf, V, 32);
+        buf[32] = sep;
+        std::memcpy(buf + 33, d_be, 32);
+        std::memcpy(buf + 65, h1, 32);
+        hmac_sha256(K, 32, buf, sizeof(buf), K);
+        hmac_sha256(K, 32, V, 32, V);
+    };
+    step(0x00);
+    step(0x01);
+    const aff* tab = static_cast<const aff*>(p256_g_table_host());
+    for (int attempt = 0; attempt < 64; ++attempt) {
+        hmac_sha256(K, 32, V, 32, V);
+        const fe k = fe_from_be(V);
+        if (!fe_is_zero(k) && !fe_geq(k, n)) {
+            aff R;
+            if (jac_to_aff(mul_g(k, tab), R)) {
+                const fe r = sc_reduce(R.x);
+                if (!fe_is_zero(r)) {
+                    // s = k^-1 (e + r d) mod n
+                    const fe k_m = sc_to_mont(k);
+                    const fe kinv_m = sc_inv_mont(k_m);                  // k^-1 R
+                    const fe rd = sc_mont_mul(sc_to_mont(r), d);         // r d
+                    fe sum;
+                    const uint32_t c = raw_add(sum, e, rd);
+                    fe red;
+                    const uint32_t br = raw_sub(red, sum, n);
+                    sum = fe_select(c || br == 0, red, sum);
+                    const fe s = sc_mont_mul(sum, kinv_m);               // (e + rd) k^-1
+                    if (!fe_is_zero(s)) {
+                        fe_to_le(r, r_le);
+                        fe_to_le(s, s_le);
+                        return true;
+                    }
+                }
+            }
+        }
+        uint8_t b2[33];
+        std::memcpy(b2, V, 32);
+        b2[32] = 0x00;
+        hmac_sha256(K, 32, b2, 33, K);
+        hmac_sha256(K, 32, V, 32, V);
+    }
+    return false;
 }
 
 }  // namespace upow

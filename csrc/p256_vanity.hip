@@ -113,11 +113,6 @@ __global__ __launch_bounds__(kVanLanesPerBlock) void p256_vanity_kernel(const ui
     if (!van_walk_run(MulG16{gtab16}, gtab16, base, start, len, w, sink)) *fail = 1u;
 }
 
-static void launch_check(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + " launch: " + hipGetErrorString(e));
-}
-
 // ------------------------------------------------------------------------------------------------
 // arguments
 // ------------------------------------------------------------------------------------------------

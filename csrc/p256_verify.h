@@ -1,8 +1,9 @@
 // The P-256 verify pieces shared by the block-latency kernels (csrc/p256.hip: four and eight lanes per
-// signature, compiled with the ILP-first scheduler) and the one-lane batch kernel (csrc/p256_batch.hip,
-// compiled with the default occupancy-first scheduler so it keeps four waves per SIMD without spilling):
-// the 160-byte work item, the scalar prologue (range checks, s^-1, u1, u2), the x-coordinate epilogue, the
-// signed 5-bit windows of u2 and the 16-bit fixed-base windows of u1*G.
+// signature, compiled with the ILP-first scheduler; their step schedule is csrc/p256_steps.h) and the one-lane
+// batch kernel (csrc/p256_batch.hip, compiled with the default occupancy-first scheduler so it keeps four
+// waves per SIMD without spilling): the 160-byte work item, the scalar prologue (range checks, s^-1, u1, u2),
+// the x-coordinate test and epilogue, the signed 5-bit windows of u2 and the 16-bit fixed-base windows of
+// u1*G; and the curve-equation checks of the key kernels (csrc/p256_keys.hip, p256_keyrec_kernel).
 //
 // reference: fastecdsa ecdsa.verify as called from upow/upow_transactions/transaction_input.py:84-120.
 #pragma once
@@ -48,17 +49,19 @@ UPOW_HD uint8_t verify_prologue(const VerifyItem& it, aff& q, fe& r, fe& u1, fe&
     return 255;                                 // continue
 }
 
-UPOW_HD uint8_t verify_epilogue(const jac& R, const fe& r) {
-    if (jac_is_inf(R)) return 0;
-    const fe z2 = fe_sqr(R.z);
-    if (fe_eq(fe_mul(r, z2), R.x)) return 1;
-    // r + n < p ?  (x(R) in [n, p) maps to x mod n = x - n)
+// x(R) == r for R with X / ZZ = x(R), ZZ != 0, without the inversion: X == r ZZ, or (r + n) ZZ when
+// r + n < p (x(R) in [n, p) maps to x mod n = x - n)
+UPOW_HD uint8_t x_matches_r(const fe& X, const fe& ZZ, const fe& r) {
+    if (fe_eq(fe_mul(r, ZZ), X)) return 1;
     fe rn;
     const uint32_t c = raw_add(rn, r, fe_const_n());
-    if (!c && !fe_geq(rn, fe_const_p())) {
-        if (fe_eq(fe_mul(rn, z2), R.x)) return 1;
-    }
+    if (!c && !fe_geq(rn, fe_const_p()) && fe_eq(fe_mul(rn, ZZ), X)) return 1;
     return 0;
+}
+
+UPOW_HD uint8_t verify_epilogue(const jac& R, const fe& r) {
+    if (jac_is_inf(R)) return 0;
+    return x_matches_r(R.x, fe_sqr(R.z), r);
 }
 
 // Signed 5-bit windows of a scalar k < 2^256 (Booth recoding): 52 digits in [-16, 16], top first, with
@@ -84,7 +87,7 @@ struct BoothW5 {
 static constexpr int kBoothWindows = 52;
 
 // The host's k*G: 32 byte windows over T[j][b] = b * 256^j * G (32 x 256 affine points, entry 0 unused; built
-// once by csrc/p256.hip, p256_g_table_host)
+// once by csrc/p256_tables.hip, p256_g_table_host)
 static constexpr int kGWin = 32;
 static constexpr int kGEnt = 256;
 UPOW_HD jac mul_g(const fe& k, const aff* tab) {
@@ -111,58 +114,19 @@ UPOW_HD jac mul_g16(const fe& k, const aff* tab16) {
     return acc;
 }
 
-// XYZZ coordinates (x = X/ZZ, y = Y/ZZZ) of the lane-group kernels (csrc/p256.hip)
-struct xz { fe x, y, zz, zzz; };  // XYZZ point; zz == 0 <=> infinity
-static_assert(sizeof(xz) == 128, "xz layout");
-
-// Jacobian (X, Y, Z) -> XYZZ (X, Y, Z^2, Z^3): the same affine point, one lane on its own
-UPOW_HD xz jac_to_xz(const jac& p) {
-    const fe zz = fe_sqr(p.z);
-    return xz{p.x, p.y, zz, fe_mul(zz, p.z)};
+// The curve equation y^2 = x^3 - 3x + b for a compressed key's x: y gets the root candidate of the right-hand
+// side; true when x < p and the candidate is a root. The caller picks the root of the wanted parity.
+UPOW_HD bool curve_y(const fe& x, fe& y) {
+    const bool good = !fe_geq(x, fe_const_p());
+    const fe x3 = fe_mul(fe_sqr(x), x);
+    const fe rhs = fe_add(fe_sub(x3, fe_add(fe_add(x, x), x)), fe_const_b());
+    y = fe_sqrt_candidate(rhs);
+    return good && fe_eq(fe_sqr(y), rhs);
 }
 
-// The arithmetic of the eight-lane kernel's pair-split product (csrc/p256.hip OctDev::mul_pair): each lane of a
-// pair (k, k + 4) runs four of the eight schoolbook rows (`split_rows`), the lower lane adds the upper lane's
-// 12-word partial sum to its own and reduces (`combine_rows`). mul_pair_host plays both lanes on one thread;
-// tests/test_p256_arith.py (check_field_binary, operation 'mul_pair' of the p256_probe hook) compares it with
-// a*b mod p on the operand pairs fe_mul gets, among them the ones whose column-11 carry runs through columns
-// 12..15, and tests/test_p256_arith_gpu.py runs the same pairs through both device builds.
-UPOW_HD void split_rows(uint32_t p[12], const fe& a, const fe& b, bool upper) {
-    uint32_t ar[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) ar[i] = upper ? a.v[4 + i] : a.v[i];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) p[i] = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        unsigned cy = 0;
-        uint32_t prev = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const uint64_t t = uint64_t(ar[i]) * b.v[j] + p[i + j];
-            p[i + j] = __builtin_addc(uint32_t(t), prev, cy, &cy);
-            prev = uint32_t(t >> 32);
-        }
-        p[i + 8] = prev + cy;
-    }
-}
-// lo: columns 0..11 of the lower rows; hi: columns 4..15 of the upper rows (hi[w] is column w + 4)
-UPOW_HD fe combine_rows(const uint32_t lo[12], const uint32_t hi[12]) {
-    uint32_t c[16];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) c[w] = lo[w];
-    unsigned cy = 0;
-#pragma unroll
-    for (int w = 4; w < 12; ++w) c[w] = __builtin_addc(lo[w], hi[w - 4], cy, &cy);
-#pragma unroll
-    for (int w = 12; w < 16; ++w) c[w] = __builtin_addc(0u, hi[w - 4], cy, &cy);
-    return fe_reduce(c);
-}
-
-UPOW_HD fe mul_pair_host(const fe& a, const fe& b) {
-    uint32_t lo[12], hi[12];
-    split_rows(lo, a, b, false);
-    split_rows(hi, a, b, true);
-    return combine_rows(lo, hi);
+// item: 64-byte full address x LE | y LE (transaction_output.py:25-26, is_point_on_curve per output)
+UPOW_HD uint8_t on_curve_64(const uint8_t* a) {
+    const aff q{fe_from_le(a), fe_from_le(a + 32)};
+    return !fe_geq(q.x, fe_const_p()) && !fe_geq(q.y, fe_const_p()) && aff_on_curve(q) ? 1 : 0;
 }
 }  // namespace upow

@@ -23,6 +23,11 @@ namespace upow {
 inline void stream_check(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
+// right after a kernel launch: the launch's own error, `what` naming the kernel
+inline void launch_check(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) throw std::runtime_error(std::string(what) + " launch: " + hipGetErrorString(e));
+}
 
 // The GPU a process's node-side work belongs to (-1: whatever the calling thread has current). A
 // multi-GPU rank sets it once (``set_node_device``), so GPU calls made from its ledger worker thread

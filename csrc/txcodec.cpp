@@ -873,7 +873,7 @@ static py::tuple block_signer_records(py::buffer pay_addr_b, py::buffer pay_len_
     return py::make_tuple(1, py::bytes(recs));
 }
 
-// The key + verify stages of the native block path fused on the GPU (p256.hip p256_verify_fused_gpu): the
+// The key + verify stages of the native block path fused on the GPU (csrc/p256.hip p256_verify_fused_gpu): the
 // signer keys go to the device compressed and are decompressed into the verify items there, next to the
 // curve check of every other 33-byte address of the block (spent outputs' owners and new outputs), and the
 // verify runs behind them in the same stream order -- no host deduplication, no decompressed keys coming

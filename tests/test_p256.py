@@ -55,18 +55,26 @@ def test_field_arithmetic_matches_python(native):
     """The kernels' field code (p256_field.h, run on the host): products, squares, sums and differences
     mod p against Python integers, and the Solinas reduction of arbitrary 512-bit values — including the
     words patterns that drive its signed overflow to both ends of [-4, 4] (the h = -1 and h = 1 folds). The
-    cases are p256_operands.legacy_field_cases, drawn as this test always drew them."""
+    cases are p256_operands.legacy_field_cases, drawn as this test always drew them; each function runs over
+    all of them in one call of the p256_probe hook's host mode (csrc/p256_probe.h)."""
     from upow_amd.ops.native import lib
     L = lib()
     p = o.P
     pairs, wide = legacy_field_cases()
     assert len(pairs) == 2011 and len(wide) == 4000
-    for a, b in pairs:
-        out = L.p256_fe_ops(a.to_bytes(32, 'little'), b.to_bytes(32, 'little'))
-        got = [int.from_bytes(out[32 * i:32 * i + 32], 'little') for i in range(4)]
-        assert got == [a * b % p, a * a % p, (a + b) % p, (a - b) % p], (hex(a), hex(b))
-    for c in wide:
-        assert int.from_bytes(L.p256_fe_reduce(c.to_bytes(64, 'little')), 'little') == c % p, hex(c)
+
+    def probe(op_name, a, b, nbytes=32):
+        out = L.p256_probe(op_name, b''.join(v.to_bytes(nbytes, 'little') for v in a),
+                           b''.join(v.to_bytes(32, 'little') for v in b), 'host')
+        assert len(out) == 32 * len(a)
+        return [int.from_bytes(out[32 * i:32 * i + 32], 'little') for i in range(len(a))]
+
+    xs, ys = [a for a, _ in pairs], [b for _, b in pairs]
+    got = zip(probe('fe_mul', xs, ys), probe('fe_sqr', xs, []), probe('fe_add', xs, ys), probe('fe_sub', xs, ys))
+    for (a, b), g in zip(pairs, got):
+        assert list(g) == [a * b % p, a * a % p, (a + b) % p, (a - b) % p], (hex(a), hex(b))
+    for c, g in zip(wide, probe('fe_reduce', wide, [], 64)):
+        assert g == c % p, hex(c)
 
 
 def test_verify_semantics(native):
@@ -263,7 +271,7 @@ def test_node_device_pin_from_worker_thread(gpu):
 
 
 def test_on_curve_batch_matches_oracle(native):
-    """Native batch on-curve check of 64-byte addresses (csrc/p256.hip p256_on_curve, host pool) against the
+    """Native batch on-curve check of 64-byte addresses (csrc/p256_keys.hip p256_on_curve, host pool) against the
     pure-int oracle: valid points, y flipped to the other root, x or y >= p, off-curve noise."""
     import random
     from upow_amd.utils import p256 as o

@@ -1,5 +1,5 @@
 """P-256 field, scalar and point arithmetic at edge operands: every function the signature kernels are built from
-(csrc/p256_field.h, the pair-split product and the lane-group step schedule of csrc/p256.hip, the signer's
+(csrc/p256_field.h, the pair-split product and the lane-group step schedule of csrc/p256_steps.h, the signer's
 madd_window) run one item at a time through the p256_probe hook and compared with Python integers.
 
 This file runs the host compile (mode 'host'; the lane-group operations through QuadHost and OctHost).

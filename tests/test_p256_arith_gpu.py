@@ -1,5 +1,5 @@
 """P-256 field, scalar and point arithmetic at edge operands on the device: the checks of test_p256_arith.py
-through the two device builds of the p256_probe hook: 'ilp' is a kernel of csrc/p256.hip (the ILP-first
+through the two device builds of the p256_probe hook: 'ilp' is a kernel of csrc/p256_probe.hip (the ILP-first
 scheduler of the block-latency kernels), 'occ' one of csrc/p256_batch.hip (the default scheduler). The lane-group
 operations (mul4, sqr4, dbl4, add4) run through QuadDev and OctDev, whose DPP broadcasts and pair split exist on
 the device only; there every lane of a group returns all it holds, and every copy must equal the expectation.

@@ -39,9 +39,10 @@ stale() {  # $1 = object, rest = inputs: rebuild when any input is newer
   for i in "$@"; do [ "$i" -nt "$o" ] && return 0; done
   return 1
 }
-HDRS="csrc/native.h csrc/sha256_common.h csrc/p256_field.h csrc/p256_verify.h csrc/p256_sign.h csrc/p256_vanity.h"
+HDRS="csrc/native.h csrc/sha256_common.h csrc/p256_field.h csrc/p256_verify.h csrc/p256_steps.h csrc/p256_probe.h csrc/p256_sign.h csrc/p256_vanity.h"
 echo "== [1] host selftest (ASan + UBSan) and host pool (TSan)"
-for h in p256 p256_batch p256_vanity; do  # the verify TU, the one-lane batch kernel's TU it launches, the vanity walk
+# the verify TU, the one-lane batch kernel's TU it launches, the fixed-base tables, decompression, the signers, the vanity walk
+for h in p256 p256_batch p256_tables p256_keys p256_sign p256_vanity; do
   if stale "$OUT/$h.o" csrc/$h.hip $HDRS; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -Xarch_host -O0 -g1 -std=c++17 -I/opt/rocm/include $SAN_HOST \
       -c csrc/$h.hip -o "$OUT/$h.o"
@@ -53,7 +54,7 @@ for f in csrc/sha256_host.cpp csrc/sha256_ni.cpp csrc/base58.cpp csrc/p256_host.
     $CXX $CFLAGS -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -c "$f" -o "$o"
   fi
 done
-$CXX -fsanitize=address,undefined -pthread "$OUT"/host_selftest.o "$OUT"/p256.o "$OUT"/p256_batch.o "$OUT"/p256_vanity.o "$OUT"/sha256_host.o \
+$CXX -fsanitize=address,undefined -pthread "$OUT"/host_selftest.o "$OUT"/p256.o "$OUT"/p256_batch.o "$OUT"/p256_tables.o "$OUT"/p256_keys.o "$OUT"/p256_sign.o "$OUT"/p256_vanity.o "$OUT"/sha256_host.o \
   "$OUT"/sha256_ni.o "$OUT"/base58.o "$OUT"/p256_host.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o "$OUT/host_selftest"
 # leak checking off: the HIP runtime keeps process-lifetime allocations
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 "$OUT/host_selftest"

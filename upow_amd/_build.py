@@ -63,12 +63,18 @@ CLANGXX = '/opt/rocm/llvm/bin/clang++'
 # instructions. The ILP-first machine scheduler interleaves independent products instead (1,810 s_nop): the
 # block-latency kernels run one wave per SIMD, so the extra registers cost them nothing; the batch kernels
 # keep their __launch_bounds__ occupancy.
-DEVICE_FLAGS = {'p256': ['-mllvm', '-amdgpu-sched-strategy=max-ilp']}  # p256_batch.hip: the default schedule
+# ILP-first stems: p256 is the verify TU (the lane-group kernels, p256_keyrec_kernel); p256_tables
+# (build_g16_kernel), p256_keys (decompression, on-curve) and p256_probe (the `ilp` and lane-group probe kernels,
+# whose point is to run the verify TU's schedule) hold kernels that were built this way as part of p256.hip
+# before it was split by subsystem, and keep their code. p256_batch, p256_sign, p256_vanity: the default schedule.
+MAX_ILP = ['-mllvm', '-amdgpu-sched-strategy=max-ilp']
+ILP_STEMS = ('p256', 'p256_tables', 'p256_keys', 'p256_probe')
+DEVICE_FLAGS = {stem: MAX_ILP for stem in ILP_STEMS}
 # A/B builds of the P-256 kernels (build-ab/native-<variant>, shipped to the GPU box and loaded through
-# UPOW_NATIVE_SO): 'p256occ' the occupancy-first schedule, 'p256bgcd' the binary-Euclid s^-1,
-# 'p256batchilp' the one-lane batch kernel under the ILP-first schedule too
-AB_VARIANTS = {'p256occ': {'p256': []}, 'p256bgcd': {'p256': DEVICE_FLAGS['p256'] + ['-DUPOW_P256_INV_BGCD=1']},
-               'p256batchilp': {'p256_batch': ['-mllvm', '-amdgpu-sched-strategy=max-ilp']}}
+# UPOW_NATIVE_SO): 'p256occ' the occupancy-first schedule for every ILP-first file, 'p256bgcd' the binary-Euclid
+# s^-1 (the verify TU only), 'p256batchilp' the one-lane batch kernel under the ILP-first schedule too
+AB_VARIANTS = {'p256occ': {stem: [] for stem in ILP_STEMS}, 'p256bgcd': {'p256': MAX_ILP + ['-DUPOW_P256_INV_BGCD=1']},
+               'p256batchilp': {'p256_batch': MAX_ILP}}
 
 
 def _device_flags(src: Path, variant: str) -> list:

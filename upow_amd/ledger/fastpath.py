@@ -127,7 +127,7 @@ def decode(tx_hexes: List[str], threads: int = 0) -> Optional[dict]:
 
 def _signer_records_general(pay, out_addr, out_len, job_input, sigs, sig_ids, digest, job_tx, gpu_min):
     """Verify records when the block has 64-byte (version-1) addresses: 33-byte keys decompressed in one
-    batch, 64-byte ones checked on the curve in one batch (csrc/p256.hip ``p256_on_curve``); None when any
+    batch, 64-byte ones checked on the curve in one batch (csrc/p256_keys.hip ``p256_on_curve``); None when any
     key is invalid."""
     all_addr = np.concatenate([pay['addr'], out_addr]) if len(out_addr) else np.ascontiguousarray(pay['addr'])
     all_len = np.concatenate([pay['len'].astype(np.uint8), out_len])

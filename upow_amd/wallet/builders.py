@@ -3,7 +3,7 @@
 reference: upow/upow_wallet/utils.py:11-613 (create_transaction, multi-send, stake, unstake,
 inode (de)registration, validator registration, voting as validator / delegate, revoking).
 Same selection rule (smallest single input covering the amount, else largest-first), same outputs,
-messages and error strings; signing uses the native RFC 6979 signer (csrc/p256.hip).
+messages and error strings; signing uses the native RFC 6979 signer (csrc/p256_sign.hip).
 """
 from __future__ import annotations
 
