@@ -624,6 +624,43 @@ PYBIND11_MODULE(_native, m) {
                               r.outputs, r.skipped, totals);
     }, py::arg("h"), py::arg("top") = -1, py::arg("by_mask") = 0x81u, py::arg("log2_groups") = 0u,
        py::arg("tag_bits") = 32u);
+    // state digest (LtHash16/1024, native.h): (state bytes[2048], entry count) of a table's live entries with a
+    // tag in tag_mask, or of records n x 40 with payloads n x 80 (None: no payload) on the GPU / on host threads
+    auto digest_out = [](const StateDigestOut& r) {
+        return py::make_tuple(py::bytes(reinterpret_cast<const char*>(r.state), sizeof r.state), r.count);
+    };
+    m.def("utxo_state_digest", [digest_out](int64_t h, uint32_t tag_mask, uint32_t grid_blocks) {
+        StateDigestOut r;
+        { py::gil_scoped_release rel; utxo_state_digest(h, tag_mask, grid_blocks, r); }
+        return digest_out(r);
+    }, py::arg("h"), py::arg("tag_mask") = 0x7fu, py::arg("grid_blocks") = 0u);
+    auto digest_args = [recs_arg](py::buffer recs, py::object payload, py::buffer_info& pi, int64_t& n,
+                                  const uint8_t*& pp) {
+        const uint8_t* p = recs_arg(recs, n);
+        pp = nullptr;
+        if (!payload.is_none()) {
+            pi = payload.cast<py::buffer>().request();
+            if (pi.size * pi.itemsize != n * 80) throw std::invalid_argument("payload must be n x 80 bytes");
+            pp = static_cast<const uint8_t*>(pi.ptr);
+        }
+        return p;
+    };
+    m.def("utxo_records_digest", [digest_out, digest_args](py::buffer recs, py::object payload, uint32_t grid_blocks) {
+        py::buffer_info pi;
+        int64_t n; const uint8_t* pp;
+        const uint8_t* p = digest_args(recs, payload, pi, n, pp);
+        StateDigestOut r;
+        { py::gil_scoped_release rel; utxo_records_digest(p, pp, n, grid_blocks, r); }
+        return digest_out(r);
+    }, py::arg("recs"), py::arg("payload") = py::none(), py::arg("grid_blocks") = 0u);
+    m.def("utxo_records_digest_host", [digest_out, digest_args](py::buffer recs, py::object payload, int threads) {
+        py::buffer_info pi;
+        int64_t n; const uint8_t* pp;
+        const uint8_t* p = digest_args(recs, payload, pi, n, pp);
+        StateDigestOut r;
+        { py::gil_scoped_release rel; utxo_records_digest_host(p, pp, n, threads, r); }
+        return digest_out(r);
+    }, py::arg("recs"), py::arg("payload") = py::none(), py::arg("threads") = 1);
     // test hooks: (home slot u32[n], K10 fingerprint u64[n]) of key records; the table's raw 48-byte slots
     m.def("utxo_debug_hashes", [recs_arg](py::buffer recs, uint32_t log2_cap) {
         int64_t n; const uint8_t* p = recs_arg(recs, n);

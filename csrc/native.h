@@ -181,6 +181,28 @@ struct OwnerTotalsOut {
 void utxo_owner_totals(int64_t h, int64_t top, uint32_t by_mask, uint32_t log2_groups, uint32_t tag_bits,
                        OwnerTotalsOut& out);
 
+// ---------------------------------------------------------------- state digest: utxo_digest.hip, utxo_digest_host.cpp
+// LtHash16/1024 of a set of entries (key record + payload): the lane-wise sum modulo 2^16 of each entry's 1024
+// lanes, and the entry count. With L = addr_len if it is 33 or 64, else 0 (then amount and flags count as 0; an
+// entry without payload has L = 0):
+//   E = txid[32] | u8(index) | u8(tag) | u8(flags & 1) | u8(L) | u64le(amount) | addr[0:L]
+//   lane[16 c + k] = the big-endian u16 at bytes 2k, 2k + 1 of SHA-256(E | u8(c)),  c in [0, 64), k in [0, 16)
+// `state` is the 1024 lanes as little-endian u16. Sums of disjoint sets add lane-wise, so the digest after a block
+// is the digest before + that of its created entries - that of its spent entries.
+// utxo_state_digest: the live entries of table h whose tag's bit is set in tag_mask (tags above 31: none), in one
+// table pass behind any queued async apply. utxo_records_digest: n host records (40 bytes) and payloads (80
+// bytes, nullptr: none) on the GPU; _host: the same on `threads` host threads, the result independent of them.
+// grid_blocks (0: the default grid, else at most 65,536) is a test lever, not set by the node.
+struct StateDigestOut {
+    uint8_t state[2048];
+    uint64_t count = 0;
+};
+void utxo_state_digest(int64_t h, uint32_t tag_mask, uint32_t grid_blocks, StateDigestOut& out);
+void utxo_records_digest(const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, uint32_t grid_blocks,
+                         StateDigestOut& out);
+void utxo_records_digest_host(const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, int threads,
+                              StateDigestOut& out);
+
 // ---------------------------------------------------------------- block input pass, K12 set hash: utxo_block.hip
 // whole-block input pass: lookup (K7) + duplicate candidates (K10) + per-tx fees (K11) in one round trip
 // Outputs of the whole-block input pass, written in place (the caller's arrays: no intermediate copies)

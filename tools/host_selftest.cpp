@@ -1,7 +1,7 @@
 // Host-side self-test of the native library's CPU paths, built with AddressSanitizer and
 // UndefinedBehaviorSanitizer by tools/sanitize_host.sh ("Build the C++ with ASan/UBSan").
 // Known-answer vectors: FIPS 180-2 SHA-256 "abc", RFC 6979 A.2.5 (P-256, SHA-256, "sample"),
-// SEC 2 generator G; everything else is a round-trip or a cross-check between two code paths.
+// SEC 2 generator G, the state digest's five sets (csrc/native.h); everything else is a round-trip or a cross-check between two code paths.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -191,6 +191,106 @@ static void test_vanity_host() {
     CHECK(threw);
 }
 
+// State digest (LtHash16/1024, csrc/utxo_digest_host.cpp): the known answers of the sets {}, {A}, {B}, {C}, {A, B, C}
+// (lanes 0..3, lane 1023, the short id SHA-256("upow-utxo-state-v1" | u64le(count) | state)), computed with
+// hashlib from the definition; the result does not depend on the thread count, the split or the order.
+static void put_entry(std::vector<uint8_t>& recs, std::vector<uint8_t>& pay, const uint8_t txid[32], uint32_t index,
+                      uint32_t tag, uint32_t flags, uint64_t amount, const std::vector<uint8_t>& addr) {
+    const size_t r = recs.size(), p = pay.size();
+    recs.resize(r + 40, 0);
+    pay.resize(p + 80, 0);
+    std::memcpy(&recs[r], txid, 32);
+    std::memcpy(&recs[r + 32], &index, 4);
+    std::memcpy(&recs[r + 36], &tag, 4);
+    const uint32_t len = uint32_t(addr.size());
+    std::memcpy(&pay[p], &amount, 8);
+    std::memcpy(&pay[p + 8], &len, 4);
+    std::memcpy(&pay[p + 12], &flags, 4);
+    if (len) std::memcpy(&pay[p + 16], addr.data(), len);
+}
+
+static std::string state_short_id(const StateDigestOut& d) {
+    std::vector<uint8_t> m;
+    const char* dom = "upow-utxo-state-v1";
+    m.insert(m.end(), dom, dom + std::strlen(dom));
+    for (int i = 0; i < 8; ++i) m.push_back(uint8_t(d.count >> (8 * i)));
+    m.insert(m.end(), d.state, d.state + sizeof d.state);
+    std::string hex;
+    char b[3];
+    for (uint8_t x : sha(m.data(), m.size())) {
+        std::snprintf(b, sizeof b, "%02x", x);
+        hex += b;
+    }
+    return hex;
+}
+
+static void test_state_digest() {
+    uint8_t ta[32], tb[32], tc[32];
+    std::vector<uint8_t> aa{42}, ab;
+    for (int i = 0; i < 32; ++i) {
+        ta[i] = uint8_t(i);
+        tb[i] = uint8_t(32 + i);
+        tc[i] = 0xff;
+        aa.push_back(uint8_t(1 + i));
+    }
+    for (int i = 0; i < 64; ++i) ab.push_back(uint8_t(100 + i));
+    struct Known {
+        int set;  // bit 0: A, bit 1: B, bit 2: C
+        uint16_t lanes[4], last;
+        const char* id;
+    };
+    const Known known[] = {
+        {0, {0, 0, 0, 0}, 0, "4577ffd454ce69e51a2270ed607b8d177f6ab4f55a4ab9ee86b35ddf0ec5701e"},
+        {1, {26070, 32850, 57441, 7641}, 5172, "c75477d194dae8dfccf51124c0ef15ba6592b7b3e62cd51f80d8549c00a2c72c"},
+        {2, {41818, 58637, 24425, 48484}, 60684, "ae5bf37023ce0473a10759302c5d2c7c50c135a99a038404b26068fafc2606f4"},
+        {4, {59715, 39545, 44934, 31578}, 42120, "171ca47560425b0c0365767be9f81f650a7c04a04f661feb57919f663bb43790"},
+        {7, {62067, 65496, 61264, 22167}, 42440, "6240967130b264ca49cfa3f850b080d1420d54710a2bdf6f430949378e3248a8"}};
+    auto lane = [](const StateDigestOut& d, int x) { return uint16_t(d.state[2 * x] | (d.state[2 * x + 1] << 8)); };
+    for (const Known& k : known) {
+        std::vector<uint8_t> recs, pay;
+        if (k.set & 1) put_entry(recs, pay, ta, 0, 0, 0, 1, aa);
+        if (k.set & 2) put_entry(recs, pay, tb, 255, 0, 1, 600000000, ab);
+        if (k.set & 4) put_entry(recs, pay, tc, 7, 6, 0, 12345, {});
+        const int64_t n = int64_t(recs.size() / 40);
+        for (int threads : {1, 3}) {
+            StateDigestOut d;
+            utxo_records_digest_host(recs.data(), pay.data(), n, threads, d);
+            CHECK(d.count == uint64_t(n));
+            for (int x = 0; x < 4; ++x) CHECK(lane(d, x) == k.lanes[x]);
+            CHECK(lane(d, 1023) == k.last);
+            CHECK(state_short_id(d) == k.id);
+        }
+    }
+    // C with a flag, an amount and three address bytes is C (nothing of a payload of unknown length is hashed), and
+    // so is C without payload
+    std::vector<uint8_t> recs, pay;
+    put_entry(recs, pay, tc, 7, 6, 1, 999, {'x', 'y', 'z'});
+    StateDigestOut d, e;
+    utxo_records_digest_host(recs.data(), pay.data(), 1, 1, d);
+    utxo_records_digest_host(recs.data(), nullptr, 1, 1, e);
+    CHECK(state_short_id(d) == known[3].id && state_short_id(e) == known[3].id);
+    // 2,000 random entries: 125 work items, enough for the pool to run them on its threads (it keeps fewer than 64
+    // on the caller), so the per-item accumulators and the locked merge run concurrently here; every thread count
+    // gives the same bytes; two parts add up
+    std::mt19937 rng(17);
+    recs.clear();
+    pay.clear();
+    for (int i = 0; i < 2000; ++i) {
+        uint8_t t[32];
+        for (auto& x : t) x = uint8_t(rng());
+        std::vector<uint8_t> addr(size_t(i % 3 == 0 ? 33 : (i % 3 == 1 ? 64 : 0)));
+        for (auto& x : addr) x = uint8_t(rng());
+        put_entry(recs, pay, t, rng() & 0xff, rng() % 7, rng() & 1, (uint64_t(rng()) << 20) | rng(), addr);
+    }
+    StateDigestOut one, many, lo, hi;
+    utxo_records_digest_host(recs.data(), pay.data(), 2000, 1, one);
+    utxo_records_digest_host(recs.data(), pay.data(), 2000, 16, many);
+    CHECK(std::memcmp(one.state, many.state, sizeof one.state) == 0 && one.count == 2000 && many.count == 2000);
+    utxo_records_digest_host(recs.data(), pay.data(), 300, 3, lo);  // 19 items: on the caller
+    utxo_records_digest_host(recs.data() + 40 * 300, pay.data() + 80 * 300, 1700, 3, hi);
+    for (int x = 0; x < 1024; ++x) CHECK(uint16_t(lane(lo, x) + lane(hi, x)) == lane(one, x));
+}
+
 static void test_pow_host() {
     PowJobHost job;
     job.header.assign(108, 0);
@@ -209,6 +309,7 @@ int main() {
     test_base58();
     test_p256();
     test_vanity_host();
+    test_state_digest();
     test_pow_host();
     if (failures) {
         std::fprintf(stderr, "%d failure(s)\n", failures);

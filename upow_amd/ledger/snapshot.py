@@ -5,7 +5,7 @@ damaged UTXO set is rebuilt by replaying every transaction (create_unspent_outpu
 SQLite ledger stays authoritative and durable; what a restart has to rebuild is the GPU index
 (every row of the seven output tables → HBM). A snapshot is the index itself:
 
-    line 1   JSON header {magic, version, height, tip_hash, count, utxo_hash, payload_sha256}
+    line 1   JSON header {magic, version, height, tip_hash, count, utxo_hash, payload_sha256, state_digest}
     then     count × 40-byte records {txid 32 B, u32 index, u32 table tag}, canonical (txid, index) order
     then     count × 80-byte payloads {u64 amount, u32 address length, pad, address[64]} (same order)
 
@@ -13,7 +13,9 @@ written atomically (tmp file + rename) at the tip. On start, :func:`try_restore`
 the snapshot's (height, tip hash) equals the ledger's tip, the payload checksum matches and the
 per-table row counts match the SQL tables; the index's K12 hash (``UtxoIndex.set_hash``) must equal
 the header's. Anything else — another chain, a partial write, a stale height — falls back to the
-full rebuild from SQL, so a bad snapshot can cost time but never correctness.
+full rebuild from SQL, so a bad snapshot can cost time but never correctness. ``state_digest`` is the short id
+of the index's state digest over all seven tables with their payloads (``UtxoIndex.state_digest().hex()``),
+for ``tools utxo-digest`` and for comparing replicas; files written before it existed load as before.
 """
 from __future__ import annotations
 
@@ -93,13 +95,39 @@ def _k12(recs: np.ndarray) -> str:
     return hashlib.sha256(np.ascontiguousarray(np.concatenate([m[:, :32], m[:, 32:33]], axis=1)).tobytes()).hexdigest()
 
 
+DIGEST_SLICE, DIGEST_THREADS = 16384, 4  # entries per host digest call of a save; threads of its own
+
+
+def _state_digest(recs: np.ndarray, pay: np.ndarray):
+    """The state digest of a save's arrays, on the host (a background save must not park the whole set in the
+    device scratch pool) and off the host worker pool: that pool runs one parallel region at a time and the
+    block path's decode uses it, so a digest of the whole set on it would hold every block up for its ~0.75 s at
+    5 M outpoints, and slices on it still starved a waiting region now and then. The set is cut into slices that
+    DIGEST_THREADS threads of the save's own digest on one thread each (``threads=1`` never enters the pool; the
+    native call releases the GIL), and the slices' digests are summed."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from .utxo import StateDigest, records_digest
+    starts = range(0, len(recs), DIGEST_SLICE)
+    digest = StateDigest()
+    if not len(starts):
+        return digest
+    with ThreadPoolExecutor(max_workers=DIGEST_THREADS, thread_name_prefix='upow-snapshot-digest') as ex:
+        for part in ex.map(lambda at: records_digest(recs[at:at + DIGEST_SLICE], pay[at:at + DIGEST_SLICE],
+                                                     device='cpu', threads=1), starts):
+            digest = digest + part
+    return digest
+
+
 def _write(path: str, height: int, tip: str, recs: np.ndarray, pay: np.ndarray) -> dict:
-    from .utxo import sort_order
+    from .utxo import ALL_TAGS_MASK, _masked, sort_order
     order = sort_order(np.ascontiguousarray(recs))
     recs, pay = np.ascontiguousarray(recs[order]), np.ascontiguousarray(pay[order])
     payload = recs.tobytes() + pay.tobytes()
+    digest = _state_digest(*_masked(recs, pay, ALL_TAGS_MASK))
     header = {'magic': MAGIC, 'version': VERSION, 'height': height, 'tip_hash': tip, 'count': int(len(recs)),
-              'utxo_hash': _k12(recs), 'payload_sha256': hashlib.sha256(payload).hexdigest()}
+              'utxo_hash': _k12(recs), 'payload_sha256': hashlib.sha256(payload).hexdigest(),
+              'state_digest': digest.hex()}
     tmp = path + '.tmp'
     with open(tmp, 'wb') as f:
         f.write(json.dumps(header, separators=(',', ':')).encode() + b'\n')

@@ -138,6 +138,147 @@ def _owners_in_order(owners: np.ndarray, top: Optional[int], by_mask: int) -> np
     return owners[np.argsort(~metric, kind='stable')[:top]]  # ~m = 2^64 - 1 - m: descending, ties by key
 
 
+# State digest (``UtxoIndex.state_digest``): LtHash16/1024 (Lewi et al., "Securing Update Propagation with
+# Homomorphic Hashing") over every live entry WITH its payload. For an entry with key (txid, index, tag) and
+# payload (amount, len, flags, addr), L = len if it is 33 or 64, else 0 (then amount and flags count as 0; an
+# entry without payload has L = 0):
+#   E = txid[32] | u8(index) | u8(tag) | u8(flags & 1) | u8(L) | u64le(amount) | addr[0:L]
+#   lane[16 c + k] = the big-endian u16 at bytes 2k, 2k + 1 of SHA-256(E | u8(c)),   c = 0..63, k = 0..15
+# The digest of a set is the lane-wise sum modulo 2^16 of its entries' 1024 lanes plus the entry count, so
+# digest(after a block) = digest(before) + digest(created) - digest(spent). 2 KB, not 32 bytes: anyone can put
+# chosen entries into the set, and a short additive hash falls to the generalised-birthday attack.
+STATE_LANES = 1024
+_STATE_DOMAIN = b'upow-utxo-state-v1'
+ALL_TAGS_MASK = 0x7f
+DIGEST_HOST_THREADS = 16
+
+
+class StateDigest:
+    """``state`` (1024 x uint16) and ``count``. ``+`` / ``-`` are lane-wise modulo 2^16 on the state and plain
+    on the count; ``tobytes()`` is the state as 1024 little-endian u16, ``hex()`` the short id
+    SHA-256(b'upow-utxo-state-v1' | u64le(count) | state)."""
+    __slots__ = ('state', 'count')
+
+    def __init__(self, state=None, count: int = 0):
+        if state is None:
+            self.state = np.zeros(STATE_LANES, dtype=np.uint16)
+        elif isinstance(state, (bytes, bytearray, memoryview)):
+            self.state = np.frombuffer(bytes(state), dtype='<u2').astype(np.uint16)
+        else:
+            self.state = np.array(state, dtype=np.uint16).ravel()
+        if self.state.shape != (STATE_LANES,):
+            raise ValueError(f'a state digest has {STATE_LANES} lanes')
+        self.count = int(count)
+
+    def __add__(self, other: 'StateDigest') -> 'StateDigest':
+        return StateDigest(self.state + other.state, self.count + other.count)  # uint16 arrays wrap
+
+    def __sub__(self, other: 'StateDigest') -> 'StateDigest':
+        return StateDigest(self.state - other.state, self.count - other.count)
+
+    def __eq__(self, other):
+        if not isinstance(other, StateDigest):
+            return NotImplemented
+        return self.count == other.count and bool((self.state == other.state).all())
+
+    def __hash__(self):
+        return hash((self.count, self.tobytes()))
+
+    def tobytes(self) -> bytes:
+        return self.state.astype('<u2').tobytes()
+
+    def hex(self) -> str:
+        import hashlib
+        return hashlib.sha256(_STATE_DOMAIN + (self.count % (1 << 64)).to_bytes(8, 'little')
+                              + self.tobytes()).hexdigest()
+
+    def __repr__(self):
+        return f'StateDigest({self.hex()}, count={self.count})'
+
+
+def _digest_arrays(recs, pay):
+    recs = np.ascontiguousarray(recs, dtype=np.uint8).reshape(-1, 40)
+    if pay is not None:
+        pay = np.ascontiguousarray(pay)
+        if pay.dtype != PAYLOAD_DTYPE:
+            pay = pay.view(np.uint8).reshape(-1).view(PAYLOAD_DTYPE)
+        if len(pay) != len(recs):
+            raise ValueError('one payload per record')
+    return recs, pay
+
+
+def state_digest_of(recs: np.ndarray, pay: Optional[np.ndarray]) -> StateDigest:
+    """The state digest of packed records + payloads (``pay=None``: every entry has L = 0) with hashlib and
+    numpy: what the ``host-py`` backend runs, and the reference the native and the HBM passes are tested
+    against."""
+    import hashlib
+    recs, pay = _digest_arrays(recs, pay)
+    n = len(recs)
+    acc = np.zeros(STATE_LANES, dtype=np.uint64)
+    raw = recs.tobytes()
+    praw = pay.tobytes() if pay is not None else None
+    lanes = bytearray(2 * STATE_LANES)
+    for i in range(n):
+        r = raw[40 * i:40 * i + 40]
+        head, amount, addr = bytes((r[32], r[36], 0, 0)), bytes(8), b''
+        if praw is not None:
+            p = praw[80 * i:80 * i + 80]
+            length = int.from_bytes(p[8:12], 'little')
+            if length in (33, 64):
+                head, amount, addr = bytes((r[32], r[36], p[12] & 1, length)), p[0:8], p[16:16 + length]
+        h = hashlib.sha256(r[:32] + head + amount + addr)
+        for c in range(64):
+            hc = h.copy()
+            hc.update(bytes((c,)))
+            lanes[32 * c:32 * c + 32] = hc.digest()
+        acc += np.frombuffer(bytes(lanes), dtype='>u2')
+    return StateDigest((acc & 0xffff).astype(np.uint16), n)
+
+
+def records_digest(recs: np.ndarray, pay: Optional[np.ndarray], device: Optional[str] = None,
+                   threads: Optional[int] = None) -> StateDigest:
+    """The state digest of packed records + payloads (a block's created or spent entries; ``pay=None``: no
+    payloads). ``device='gpu'``: the records kernel of csrc/utxo_digest.hip; ``'cpu'``: the native host routine
+    (csrc/utxo_digest_host.cpp) on ``threads`` (default 16) threads of the host worker pool, or
+    :func:`state_digest_of` when the extension is not built. ``None``: the GPU when there is one. With
+    ``threads=1`` the host routine runs on the calling thread and leaves the pool alone."""
+    recs, pay = _digest_arrays(recs, pay)
+    if device is None:
+        from ..ops.native import gpu_available
+        device = 'gpu' if gpu_available() else 'cpu'
+    if device not in ('gpu', 'cpu'):
+        raise ValueError("device is 'gpu', 'cpu' or None")
+    praw = None if pay is None else pay.view(np.uint8)
+    if device == 'gpu':
+        from ..ops.native import require_gpu
+        return StateDigest(*require_gpu().utxo_records_digest(recs, praw))
+    try:
+        from ..ops.native import lib
+        fn = lib().utxo_records_digest_host
+    except (ImportError, AttributeError):
+        return state_digest_of(recs, pay)
+    return StateDigest(*fn(recs, praw, DIGEST_HOST_THREADS if threads is None else int(threads)))
+
+
+def _tag_mask(tags) -> int:
+    """Argument check of ``state_digest``: the tables to cover as a bit mask (``None``: tags 0..6)."""
+    if tags is None:
+        return ALL_TAGS_MASK
+    mask = 0
+    for t in tags:
+        if not isinstance(t, (int, np.integer)) or not 0 <= t <= 31:
+            raise ValueError(f'no table tag {t!r}: tags are 0..31')
+        mask |= 1 << int(t)
+    return mask
+
+
+def _masked(recs: np.ndarray, pay: np.ndarray, mask: int):
+    """The entries of (recs, pay) whose tag's bit is set in ``mask``."""
+    tags = np.ascontiguousarray(recs[:, 36:40]).view('<u4').ravel() if len(recs) else np.zeros(0, np.uint32)
+    keep = (tags < 32) & (((np.uint32(mask) >> np.minimum(tags, 31).astype(np.uint32)) & np.uint32(1)) != 0)
+    return np.ascontiguousarray(recs[keep]), np.ascontiguousarray(pay[keep])
+
+
 def pack_records(keys: Sequence[Outpoint], tags=None) -> np.ndarray:
     """40-byte records {txid raw 32 B, u32 index, u32 tag} for the native table."""
     n = len(keys)
@@ -242,6 +383,10 @@ class _HostBackend:
         """Every owner's record and the whole-set info, grouped on the host (``owner_totals_of``)."""
         return owner_totals_of(*self.records_payload())
 
+    def state_digest(self, tag_mask, grid_blocks=0):
+        """The state digest of the entries with a tag in ``tag_mask``: the reference (``state_digest_of``)."""
+        return state_digest_of(*_masked(*self.records_payload(), tag_mask))
+
     def __len__(self):
         return len(self.d)
 
@@ -316,6 +461,12 @@ class _NativeHostBackend:
     def owner_totals(self, top, by_mask, log2_groups=0, tag_bits=32):
         """Every owner's record and the whole-set info, grouped on the host (``owner_totals_of``)."""
         return owner_totals_of(*self.records_payload())
+
+    def state_digest(self, tag_mask, grid_blocks=0):
+        """The state digest of the entries with a tag in ``tag_mask``: a dump, then the native host routine
+        (``utxo_records_digest_host``) on the host pool."""
+        recs, pay = _masked(*self.records_payload(), tag_mask)
+        return StateDigest(*self.L.utxo_records_digest_host(recs, pay.view(np.uint8), DIGEST_HOST_THREADS))
 
     def __len__(self):
         return len(self.t)
@@ -476,6 +627,12 @@ class _GpuBackend:
         info = {'owners': int(owners), 'outputs': int(outputs), 'skipped': int(skipped),
                 'totals': np.asarray(totals, dtype=np.uint64)}
         return np.frombuffer(raw, dtype=OWNER_DTYPE), info
+
+    def state_digest(self, tag_mask, grid_blocks=0):
+        """The state digest of the live entries with a tag in ``tag_mask`` from ONE pass over the HBM table
+        (``utxo_state_digest``: live slots queued per wave, 1 + 64 SHA-256 compressions per entry, the lanes
+        summed across each wave in registers); 8 stripes of lane sums (33 KB) come back. ``grid_blocks``: test lever."""
+        return StateDigest(*self.L.utxo_state_digest(self.h, tag_mask, grid_blocks))
 
     def records_payload(self):
         raw, pay = self.L.utxo_dump_payload(self.h)
@@ -732,6 +889,16 @@ class UtxoIndex:
         mask = _by_mask(top, by)
         owners, info = self.be.owner_totals(top, mask, log2_groups, tag_bits)
         return _owners_in_order(owners, top, mask), info
+
+    @_locked
+    def state_digest(self, tags: Optional[Iterable[int]] = None, *, grid_blocks: int = 0) -> StateDigest:
+        """The state digest (:class:`StateDigest`, LtHash16/1024) of every live entry of the tables ``tags``
+        (``None``: all seven) with its payload: one value that a wrong amount, address, stake flag, tag or
+        index changes, and that adds up: after a block it is the digest before + ``records_digest`` of the
+        created entries - ``records_digest`` of the spent ones. GPU backend: one pass over the HBM table
+        behind any queued block apply (``grid_blocks`` sizes its launch: a test lever); host backends: a dump
+        and 65 compressions per entry on the CPU."""
+        return self.be.state_digest(_tag_mask(tags), grid_blocks)
 
     @_locked
     def records_payload(self, sort: bool = True):

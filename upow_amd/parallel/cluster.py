@@ -168,7 +168,10 @@ class Cluster:
 
     def status(self, db, deep: bool = False, mempool: Optional[int] = None) -> List[dict]:
         """Collective: every rank's height, tip hash and UTXO-set hash. The hash comes from the HBM index
-        (K12: compaction + radix sort on the device, host SHA tail), current at the commit point; ``deep``
+        (K12: compaction + radix sort on the device, host SHA tail), current at the commit point.
+        ``state_digest`` is the short id of the index's state digest (``UtxoIndex.state_digest``: all seven
+        tables with amounts, addresses and stake flags): one table pass on the GPU backend, so always there;
+        on a host backend 65 SHA-256 compressions per entry on the CPU, so only under ``deep``. ``deep``
         also hashes the SQL replica after the materialisers have caught up (the slow full-table audit, on
         the long-timeout group: it may take longer than the op timeout on a big ledger)."""
         mine = {'rank': self.ctx.rank, 'height': db._tip_id(), 'tip_hash': _tip_hash(db),
@@ -177,6 +180,7 @@ class Cluster:
                 # process CPU seconds (every thread) so far: what each replica costs the host, per op stream
                 'lean': bool(db.lean), 'cpu_s': round(time.process_time(), 4),
                 'crypto_cpu_s': round(_pagesync_stats().get('plan_crypto_cpu_s', 0.0), 4)}
+        mine.update(_state_digest_entry(db, deep))
         if deep:
             db.flush()
             mine['sql_utxo_hash'] = db.sql_unspent_outputs_hash()
@@ -567,12 +571,20 @@ async def mirror_delete(db, offset: int):
         c.agree_state(db, f'delete from {offset}')
 
 
+def _state_digest_entry(db, deep: bool) -> dict:
+    """The ``state_digest`` key of a rank's status: on the GPU backend always, on a host backend under ``deep``."""
+    if db.utxo.backend_name != 'gpu' and not deep:
+        return {}
+    return {'state_digest': db.utxo.state_digest().hex()}
+
+
 async def status_all(db, deep: bool = False) -> List[dict]:
     """``GET /cluster_info``: every replica's state (owner thread: the ledger thread)."""
     c = active_leader()
     if c is None:
         return [{'rank': 0, 'height': db._tip_id(), 'tip_hash': _tip_hash(db),
-                 'utxo_hash': db.utxo.set_hash(_utxo_tag()), 'utxo_entries': len(db.utxo)}]
+                 'utxo_hash': db.utxo.set_hash(_utxo_tag()), 'utxo_entries': len(db.utxo),
+                 **_state_digest_entry(db, deep)}]
     # the leader's mempool keeps admitting on the HTTP loop: its size is read together with the outbox
     # drain, under the index lock the admissions hold, so it is the size the followers reach at this op
     mp = db._mempool()

@@ -15,6 +15,13 @@ holder ascending by key, or with ``--top N`` the N greatest by the sum of the ``
 ``spendable,stake``). The holder lines go to ``--out FILE`` when given; the last line printed is the summary
 ``{"holders", "outputs", "skipped", "totals", "backend"}`` over the whole set. Exit status 1 when entries were
 skipped (indexed without their payload, so nobody can be credited with them).
+``python -m upow_amd.tools utxo-digest [--db PATH] [--snapshot FILE] [--full]``: the state digest of the UTXO index
+(``UtxoIndex.state_digest``: LtHash16/1024 over every live entry of all seven tables WITH its amount, address and
+stake flag; on a GPU node one pass over the HBM table, ``utxo_state_digest``). One JSON line ``{"digest", "entries",
+"backend", "seconds"}``, ``digest`` being the short id; ``--full`` adds ``"state"``, the 2048 bytes as hex. Two
+replicas, or a replica and a snapshot, hold the same set exactly when their lines agree. With ``--snapshot FILE`` the
+line also carries ``"snapshot_digest"`` (of the file's records and payloads, ``records_digest``) and ``"match"``;
+exit status 1 on a mismatch.
 ``python -m upow_amd.tools materialise --db <rankN ledger>``: bring a lean cluster follower's SQL tables to its
 tip from its op log (ledger/lean.py); every other command does this first when the ledger has an op log.
 ``python -m upow_amd.tools sign-batch --keys F --digests F --out F [--device gpu|cpu]``: bulk RFC 6979 signing
@@ -107,6 +114,28 @@ async def holders(top: int = None, by=('spendable', 'stake'), path: str = None, 
                    'backend': db.utxo.backend_name}
 
 
+async def utxo_digest(path: str = None, snapshot_path: str = None, full: bool = False, db: Database = None) -> dict:
+    """The ``utxo-digest`` command's line: the state digest of the index over all seven tables, and with
+    ``snapshot_path`` that of the snapshot file's records and payloads next to it."""
+    import time
+
+    from .ledger.utxo import ALL_TAGS_MASK, _masked, records_digest
+    db = db or await open_ledger(path)
+    t = time.perf_counter()
+    d = db.utxo.state_digest()
+    res = {'digest': d.hex(), 'entries': d.count, 'backend': db.utxo.backend_name,
+           'seconds': round(time.perf_counter() - t, 6)}
+    if full:
+        res['state'] = d.tobytes().hex()
+    if snapshot_path:
+        from .ledger import snapshot
+        _, recs, pay = snapshot.read(snapshot_path)
+        sd = records_digest(*_masked(recs, pay, ALL_TAGS_MASK))
+        res['snapshot_digest'] = sd.hex()
+        res['match'] = sd == d
+    return res
+
+
 async def rebuild_utxo(path: str = None):
     db = await open_ledger(path)
     outputs = await db.get_unspent_outputs_from_all_transactions()
@@ -164,7 +193,7 @@ def vanity_keys(prefix: str, ignore_case: bool = False, count: int = 1, max_keys
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('command', choices=['rebuild-utxo', 'utxo-hash', 'snapshot', 'verify-utxo', 'address-utxos',
-                                        'holders', 'materialise', 'sign-batch', 'vanity'])
+                                        'holders', 'materialise', 'sign-batch', 'vanity', 'utxo-digest'])
     ap.add_argument('address', nargs='*')
     ap.add_argument('--db', default=None)
     ap.add_argument('--out', default=None)
@@ -176,6 +205,8 @@ def main(argv=None):
     ap.add_argument('--ignore-case', action='store_true')
     ap.add_argument('--count', type=int, default=1)
     ap.add_argument('--max-keys', type=int, default=None)
+    ap.add_argument('--snapshot', default=None)
+    ap.add_argument('--full', action='store_true')
     a = ap.parse_args(argv)
     if a.command == 'sign-batch':
         if not (a.keys and a.digests and a.out):
@@ -220,6 +251,13 @@ def main(argv=None):
                 out.close()
         print(json.dumps(summary))
         return 1 if summary['skipped'] else 0
+    elif a.command == 'utxo-digest':
+        try:
+            res = asyncio.run(utxo_digest(a.db, a.snapshot, a.full))
+        except (ValueError, OSError) as e:
+            raise SystemExit(f'utxo-digest: {e}')
+        print(json.dumps(res))
+        return 0 if res.get('match', True) else 1
     elif a.command == 'rebuild-utxo':
         asyncio.run(rebuild_utxo(a.db))
     elif a.command in ('snapshot', 'verify-utxo'):
