@@ -661,6 +661,21 @@ PYBIND11_MODULE(_native, m) {
         { py::gil_scoped_release rel; utxo_records_digest_host(p, pp, n, threads, r); }
         return digest_out(r);
     }, py::arg("recs"), py::arg("payload") = py::none(), py::arg("threads") = 1);
+    // UTXO diff (native.h): (status u8[n], extra records, extra payloads, extra, repeated, live, wait s, hold s)
+    m.def("utxo_diff", [digest_args](int64_t h, py::buffer recs, py::object payload, uint32_t tag_mask, uint32_t limit,
+                                     uint32_t chunk_records) {
+        py::buffer_info pi;
+        int64_t n; const uint8_t* pp;
+        const uint8_t* p = digest_args(recs, payload, pi, n, pp);
+        UtxoDiffOut r;
+        { py::gil_scoped_release rel; utxo_diff(h, p, pp, n, tag_mask, limit, chunk_records, r); }
+        py::array_t<uint8_t> status(py::ssize_t(r.status.size()));
+        if (!r.status.empty()) std::memcpy(status.mutable_data(), r.status.data(), r.status.size());
+        return py::make_tuple(status, py::bytes(reinterpret_cast<const char*>(r.extra_recs.data()), r.extra_recs.size()),
+                              py::bytes(reinterpret_cast<const char*>(r.extra_pay.data()), r.extra_pay.size()), r.extra,
+                              r.repeated, r.live, r.wait_seconds, r.hold_seconds);
+    }, py::arg("h"), py::arg("recs"), py::arg("payload") = py::none(), py::arg("tag_mask") = 0x7fu,
+       py::arg("limit") = 65536u, py::arg("chunk_records") = 0u);
     // test hooks: (home slot u32[n], K10 fingerprint u64[n]) of key records; the table's raw 48-byte slots
     m.def("utxo_debug_hashes", [recs_arg](py::buffer recs, uint32_t log2_cap) {
         int64_t n; const uint8_t* p = recs_arg(recs, n);

@@ -203,6 +203,24 @@ void utxo_records_digest(const uint8_t* recs, const uint8_t* pay_or_null, int64_
 void utxo_records_digest_host(const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, int threads,
                               StateDigestOut& out);
 
+// ---------------------------------------------------------------- UTXO diff: utxo_diff.hip
+// Which entries differ between table h and n host records (40 bytes) with payloads (80 bytes, nullptr: none), an
+// entry being what the state digest hashes (E above) and the outpoint (txid, index) alone its identity. status[i]
+// of record i: 0 the table holds the same E, 1 the outpoint is not live, 2 it is live with another E (a tag outside
+// tag_mask included). An extra is a live entry with a tag in tag_mask that no record names: min(extra, limit) of
+// them come back, which ones and in what order is not specified; the counts are exact. `repeated` is the number of
+// records that name a live outpoint another record named already. The records go up in chunks of chunk_records
+// (0: 2^20; a test lever) under ONE hold of the table lock, behind any queued async apply, so the whole diff sees
+// one table state; hold_seconds is that hold and wait_seconds the wait for it. The table is only read.
+struct UtxoDiffOut {
+    std::vector<uint8_t> status;                 // per record: 0 same, 1 missing, 2 changed
+    std::vector<uint8_t> extra_recs, extra_pay;  // min(extra, limit) entries, any order
+    uint64_t extra = 0, repeated = 0, live = 0;  // exact; live = the table's entries with a tag in tag_mask
+    double wait_seconds = 0, hold_seconds = 0;
+};
+void utxo_diff(int64_t h, const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, uint32_t tag_mask,
+               uint32_t limit, uint32_t chunk_records, UtxoDiffOut& out);
+
 // ---------------------------------------------------------------- block input pass, K12 set hash: utxo_block.hip
 // whole-block input pass: lookup (K7) + duplicate candidates (K10) + per-tx fees (K11) in one round trip
 // Outputs of the whole-block input pass, written in place (the caller's arrays: no intermediate copies)

@@ -1139,9 +1139,10 @@ class Database:
         files = {file_of(f'{b:02x}', nt) for b in range(lo, hi)}
         return f'{self.tx_schemas[files.pop()]}.transactions' if len(files) == 1 else None
 
-    def _rebuild_utxo_index(self):
-        """Rebuild the HBM/host UTXO set from the output tables; each entry's payload (amount,
-        address bytes) comes from its creating tx's JSON columns, read with SQLite's json_extract."""
+    def _utxo_entries_from_sql(self):
+        """(outpoints, tags, payloads) of the seven output tables, one bulk query per table (per UTXO file for
+        unspent_outputs); each entry's payload (amount, address bytes) comes from its creating tx's JSON columns,
+        read with SQLite's json_extract."""
         keys, tags, amounts, addrs, stake = [], [], [], [], []
         am = 'json_extract(t.outputs_amounts, \'$[\' || u."index" || \']\')'
         ad = 'json_extract(t.outputs_addresses, \'$[\' || u."index" || \']\')'
@@ -1171,7 +1172,18 @@ class Database:
                 amounts.append(r[2])
                 addrs.append(_addr_bytes(r[3]))
                 stake.append(r[4] == 1)
-        self.utxo.reset(keys, tags, make_payload(amounts, addrs, stake))
+        return keys, tags, make_payload(amounts, addrs, stake)
+
+    def _utxo_arrays_from_sql(self):
+        """The SQL tables' UTXO set as packed (records, payloads): what the index holds when it agrees with them
+        (``tools utxo-diff --sql``)."""
+        from .utxo import pack_records
+        keys, tags, pay = self._utxo_entries_from_sql()
+        return pack_records(keys, tags), pay
+
+    def _rebuild_utxo_index(self):
+        """Rebuild the HBM/host UTXO set from the output tables (``_utxo_entries_from_sql``)."""
+        self.utxo.reset(*self._utxo_entries_from_sql())
         if getattr(self, 'gov', None) is not None:
             self.gov.rebuild()
 

@@ -272,11 +272,197 @@ def _tag_mask(tags) -> int:
     return mask
 
 
+def _record_words(recs: np.ndarray) -> np.ndarray:
+    """Packed records (n x 40 bytes) as n x 10 little-endian words (no copy when they are contiguous): the txid's
+    eight, the index, the tag."""
+    return np.ascontiguousarray(recs, dtype=np.uint8).reshape(-1, 40).view('<u4')
+
+
 def _masked(recs: np.ndarray, pay: np.ndarray, mask: int):
-    """The entries of (recs, pay) whose tag's bit is set in ``mask``."""
-    tags = np.ascontiguousarray(recs[:, 36:40]).view('<u4').ravel() if len(recs) else np.zeros(0, np.uint32)
-    keep = (tags < 32) & (((np.uint32(mask) >> np.minimum(tags, 31).astype(np.uint32)) & np.uint32(1)) != 0)
-    return np.ascontiguousarray(recs[keep]), np.ascontiguousarray(pay[keep])
+    """The entries of (recs, pay) whose tag's bit is set in ``mask`` (``pay`` may be None)."""
+    tags = _record_words(recs)[:, 9]
+    keep = np.array([(mask >> t) & 1 for t in range(32)] + [0], dtype=bool)[np.minimum(tags, 32)]
+    if keep.all():  # the usual case (every table asked for): no 120-byte-per-entry copy
+        return np.ascontiguousarray(recs), None if pay is None else np.ascontiguousarray(pay)
+    return np.ascontiguousarray(recs[keep]), None if pay is None else np.ascontiguousarray(pay[keep])
+
+
+# UTXO diff (``UtxoIndex.diff_records``): WHERE the index and a record set differ, an entry being what the state
+# digest hashes (E above) and the outpoint (txid, index) alone its identity. Of the index I against the other set O:
+# ``missing`` are the outpoints of O that I lacks, ``extra`` those of I that O lacks, ``changed`` those in both whose
+# E differ (tag, stake flag, L, amount or addr[0:L]; bytes past L, other flag bits and the amount or flag of an
+# L = 0 entry do not count). For O without repeated outpoints the diff is empty exactly when the digests agree.
+DIFF_LIMIT = 65536
+
+
+class UtxoDiff:
+    """``missing = (recs, pay)`` and ``extra = (recs, pay)``; ``changed = (recs_other, pay_other, recs_index,
+    pay_index)``, row-aligned; each list in canonical (txid, index) order and at most ``limit`` long. The counts
+    ``n_missing``, ``n_extra``, ``n_changed`` are exact; ``compared`` is the entries of O and ``entries`` the live
+    entries of I that took part; ``truncated``: some list is shorter than its count."""
+    __slots__ = ('missing', 'extra', 'changed', 'n_missing', 'n_extra', 'n_changed', 'compared', 'entries', 'info')
+
+    def __init__(self, missing, extra, changed, n_missing, n_extra, n_changed, compared, entries, info=None):
+        self.missing, self.extra, self.changed = _in_order(*missing), _in_order(*extra), _in_order(*changed)
+        self.n_missing, self.n_extra, self.n_changed = int(n_missing), int(n_extra), int(n_changed)
+        self.compared, self.entries = int(compared), int(entries)
+        self.info = info or {}  # what the backend measured (GPU: the table lock's wait and hold in seconds)
+
+    @property
+    def truncated(self) -> bool:
+        return (len(self.missing[0]) < self.n_missing or len(self.extra[0]) < self.n_extra
+                or len(self.changed[0]) < self.n_changed)
+
+    @property
+    def equal(self) -> bool:
+        return self.n_missing == 0 and self.n_extra == 0 and self.n_changed == 0
+
+    def __repr__(self):
+        return (f'UtxoDiff(missing={self.n_missing}, extra={self.n_extra}, changed={self.n_changed}, '
+                f'compared={self.compared}, entries={self.entries}, truncated={self.truncated})')
+
+
+def _in_order(recs, *rest):
+    """Row-aligned arrays sorted by the first one's canonical (txid, index) order."""
+    recs = np.ascontiguousarray(recs, dtype=np.uint8).reshape(-1, 40)
+    order = sort_order(recs)
+    return (np.ascontiguousarray(recs[order]),) + tuple(np.ascontiguousarray(x[order]) for x in rest)
+
+
+def _diff_arrays(recs, pay):
+    """Argument check of a diff's record set: (records n x 40, payloads n or None)."""
+    recs, pay = _digest_arrays(recs, pay)
+    if len(recs):
+        words = _record_words(recs)
+        if words[:, 8].max() > 255 or words[:, 9].max() > 31:
+            raise ValueError('a record has an index above 255 or a tag above 31')
+    return recs, pay
+
+
+def _entries(recs: np.ndarray, pay: Optional[np.ndarray]):
+    """(33-byte outpoint, canonical bytes E) of each entry."""
+    raw = recs.tobytes()
+    praw = pay.tobytes() if pay is not None else None
+    out = []
+    for i in range(len(recs)):
+        r = raw[40 * i:40 * i + 40]
+        head, amount, addr = bytes((r[36], 0, 0)), bytes(8), b''
+        if praw is not None:
+            p = praw[80 * i:80 * i + 80]
+            length = int.from_bytes(p[8:12], 'little')
+            if length in (33, 64):
+                head, amount, addr = bytes((r[36], p[12] & 1, length)), p[0:8], p[16:16 + length]
+        out.append((r[:33], r[:33] + head + amount + addr))
+    return out
+
+
+def _rows(recs, pay, rows):
+    rows = np.asarray(rows, dtype=np.intp)
+    return recs[rows], (pay[rows] if pay is not None else np.zeros(len(rows), dtype=PAYLOAD_DTYPE))
+
+
+def diff_of(recs_a: np.ndarray, pay_a: Optional[np.ndarray], recs_b: np.ndarray, pay_b: Optional[np.ndarray], *,
+            tag_mask: Optional[int] = None, limit: Optional[int] = None) -> UtxoDiff:
+    """The diff of the set b (the index's side) against the set a (the other side; ``pay=None``: every entry has
+    L = 0) from the definition, with dicts over the canonical bytes: what the ``host-py`` backend runs, and the
+    reference that ``diff_vectorised`` and the HBM pass are tested against. ``missing`` is in a and not in b,
+    ``extra`` in b and not in a. An outpoint that a repeats is reported missing once per occurrence when b lacks
+    it and is a ``ValueError`` when b has it.
+    With ``tag_mask`` a is first cut to the tags in the mask and an entry of b outside the mask is never extra,
+    but still makes its outpoint in a ``changed``. ``limit`` caps each list (the first ones in a's order; for
+    ``extra`` in b's)."""
+    recs_a, pay_a = _diff_arrays(recs_a, pay_a)
+    recs_b, pay_b = _digest_arrays(recs_b, pay_b)
+    if tag_mask is not None:
+        recs_a, pay_a = _masked(recs_a, pay_a, tag_mask)
+    where = {}
+    ents_b = _entries(recs_b, pay_b)
+    for j, (key, _) in enumerate(ents_b):
+        if key in where:
+            raise ValueError('the index side holds an outpoint twice')
+        where[key] = j
+    seen, missing, changed = set(), [], []
+    for i, (key, e) in enumerate(_entries(recs_a, pay_a)):
+        j = where.get(key)
+        if j is None:
+            missing.append(i)
+            continue
+        if j in seen:
+            raise ValueError(f'outpoint {key[:32].hex()}:{key[32]} appears more than once and is live in the index')
+        seen.add(j)
+        if ents_b[j][1] != e:
+            changed.append((i, j))
+    in_mask = [j for j, tag in enumerate(_record_words(recs_b)[:, 9].tolist())
+               if tag_mask is None or (tag < 32 and (tag_mask >> tag) & 1)]
+    extra = [j for j in in_mask if j not in seen]
+    n = (len(missing), len(extra), len(changed))
+    if limit is not None:
+        missing, extra, changed = missing[:limit], extra[:limit], changed[:limit]
+    return UtxoDiff(_rows(recs_a, pay_a, missing), _rows(recs_b, pay_b, extra),
+                    _rows(recs_a, pay_a, [i for i, _ in changed]) + _rows(recs_b, pay_b, [j for _, j in changed]),
+                    *n, len(recs_a), len(in_mask))
+
+
+def _canonical(recs: np.ndarray, pay: Optional[np.ndarray]):
+    """E's payload part per entry, vectorised: (tag | flag << 8 | L << 16, amount, addr with the bytes past L
+    zeroed)."""
+    n = len(recs)
+    tag = recs[:, 36].astype(np.uint32)
+    if pay is None:
+        return tag, np.zeros(n, np.uint64), np.zeros((n, 64), np.uint8)
+    length = np.where((pay['len'] == 33) | (pay['len'] == 64), pay['len'], 0).astype(np.uint32)
+    flag = np.where(length > 0, pay['flags'] & 1, 0).astype(np.uint32)
+    addr = pay['addr'].reshape(n, 64) * (np.arange(64, dtype=np.uint32)[None, :] < length[:, None])
+    return tag | (flag << 8) | (length << 16), np.where(length > 0, pay['amount'], 0).astype(np.uint64), addr
+
+
+def diff_vectorised(recs_a: np.ndarray, pay_a: Optional[np.ndarray], recs_b: np.ndarray, pay_b: Optional[np.ndarray], *,
+                    tag_mask: Optional[int] = None, limit: Optional[int] = None) -> UtxoDiff:
+    """:func:`diff_of` in numpy, for sets of millions: b is sorted by a 64-bit head of the outpoint (the txid's
+    first eight bytes mixed with the index), a's heads are looked up in it and every candidate pair is compared in
+    full. Two outpoints of b with one head, or a head that matches under another outpoint, send the whole call to
+    :func:`diff_of`, so the answer never depends on the heads. What the native host backend runs."""
+    recs_a, pay_a = _diff_arrays(recs_a, pay_a)
+    recs_b, pay_b = _digest_arrays(recs_b, pay_b)
+    if tag_mask is not None:
+        recs_a, pay_a = _masked(recs_a, pay_a, tag_mask)
+
+    def heads(recs):
+        w = _record_words(recs)
+        return ((w[:, 0].astype(np.uint64) << np.uint64(32)) | w[:, 1]) ^ \
+            ((w[:, 8] & np.uint32(0xff)).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15))
+    head_b = heads(recs_b)
+    order = np.argsort(head_b, kind='stable')
+    sorted_b = head_b[order]
+    if (sorted_b[1:] == sorted_b[:-1]).any():
+        return diff_of(recs_a, pay_a, recs_b, pay_b, tag_mask=tag_mask, limit=limit)
+    head_a = heads(recs_a)
+    order_a = np.argsort(head_a, kind='stable')  # sorted needles: the search walks sorted_b once, not at random
+    at = np.empty(len(head_a), dtype=np.intp)
+    at[order_a] = np.minimum(np.searchsorted(sorted_b, head_a[order_a]), max(len(sorted_b) - 1, 0))
+    hit = sorted_b[at] == head_a if len(sorted_b) else np.zeros(len(recs_a), bool)
+    rows_a = np.flatnonzero(hit)
+    rows_b = order[at[rows_a]]
+    if (recs_a[rows_a, :33] != recs_b[rows_b, :33]).any():
+        return diff_of(recs_a, pay_a, recs_b, pay_b, tag_mask=tag_mask, limit=limit)
+    seen = np.zeros(len(recs_b), bool)
+    seen[rows_b] = True
+    if int(seen.sum()) != len(rows_b):
+        raise ValueError(f'{len(rows_b) - int(seen.sum())} record(s) repeat an outpoint that is live in the index')
+    head_x, amount_x, addr_x = _canonical(recs_a[rows_a], None if pay_a is None else pay_a[rows_a])
+    head_y, amount_y, addr_y = _canonical(recs_b[rows_b], None if pay_b is None else pay_b[rows_b])
+    differ = (head_x != head_y) | (amount_x != amount_y) | (addr_x != addr_y).any(axis=1)
+    tags_b = _record_words(recs_b)[:, 9]
+    counted = np.ones(len(recs_b), bool) if tag_mask is None else \
+        np.array([(tag_mask >> t) & 1 for t in range(32)] + [0], dtype=bool)[np.minimum(tags_b, 32)]
+    missing, extra = np.flatnonzero(~hit), np.flatnonzero(counted & ~seen)
+    changed_a, changed_b = rows_a[differ], rows_b[differ]
+    n = (len(missing), len(extra), len(changed_a))
+    if limit is not None:
+        missing, extra, changed_a, changed_b = missing[:limit], extra[:limit], changed_a[:limit], changed_b[:limit]
+    return UtxoDiff(_rows(recs_a, pay_a, missing), _rows(recs_b, pay_b, extra),
+                    _rows(recs_a, pay_a, changed_a) + _rows(recs_b, pay_b, changed_b),
+                    *n, len(recs_a), int(counted.sum()))
 
 
 def pack_records(keys: Sequence[Outpoint], tags=None) -> np.ndarray:
@@ -387,6 +573,10 @@ class _HostBackend:
         """The state digest of the entries with a tag in ``tag_mask``: the reference (``state_digest_of``)."""
         return state_digest_of(*_masked(*self.records_payload(), tag_mask))
 
+    def diff(self, recs, pay, tag_mask, limit, chunk_records=0):
+        """The index against the record set: the reference (``diff_of``) on a dump."""
+        return diff_of(recs, pay, *self.records_payload(), tag_mask=tag_mask, limit=limit)
+
     def __len__(self):
         return len(self.d)
 
@@ -467,6 +657,10 @@ class _NativeHostBackend:
         (``utxo_records_digest_host``) on the host pool."""
         recs, pay = _masked(*self.records_payload(), tag_mask)
         return StateDigest(*self.L.utxo_records_digest_host(recs, pay.view(np.uint8), DIGEST_HOST_THREADS))
+
+    def diff(self, recs, pay, tag_mask, limit, chunk_records=0):
+        """The index against the record set: a dump, then the join in numpy (``diff_vectorised``)."""
+        return diff_vectorised(recs, pay, *self.records_payload(), tag_mask=tag_mask, limit=limit)
 
     def __len__(self):
         return len(self.t)
@@ -633,6 +827,27 @@ class _GpuBackend:
         (``utxo_state_digest``: live slots queued per wave, 1 + 64 SHA-256 compressions per entry, the lanes
         summed across each wave in registers); 8 stripes of lane sums (33 KB) come back. ``grid_blocks``: test lever."""
         return StateDigest(*self.L.utxo_state_digest(self.h, tag_mask, grid_blocks))
+
+    def diff(self, recs, pay, tag_mask, limit, chunk_records=0):
+        """The index against the record set (tags in ``tag_mask`` only) from ONE pass over the HBM table
+        (``utxo_diff``: the records go up in chunks and probe the table, each hit is compared in place and marks
+        its slot in a bitmap, then a sweep over the slots compacts the live ones nobody marked): one status byte
+        per record and at most ``limit`` extras come back. The index side of the changed entries is one
+        ``utxo_lookup`` of those records."""
+        status, xr, xp, extra, repeated, live, wait, hold = self.L.utxo_diff(
+            self.h, recs, None if pay is None else pay.view(np.uint8), tag_mask, limit, chunk_records)
+        if repeated:
+            raise ValueError(f'{repeated} record(s) repeat an outpoint that is live in the index')
+        miss, chg = np.flatnonzero(status == 1), np.flatnonzero(status == 2)
+        n_missing, n_changed = len(miss), len(chg)
+        other = _rows(recs, pay, chg[:limit])
+        mine = np.array(other[0])
+        tags, mine_pay = self.lookup_records(mine) if len(mine) else (np.zeros(0, np.uint8), np.zeros(0, PAYLOAD_DTYPE))
+        mine[:, 36] = tags
+        return UtxoDiff(_rows(recs, pay, miss[:limit]),
+                        (np.frombuffer(xr, dtype=np.uint8).reshape(-1, 40), np.frombuffer(xp, dtype=PAYLOAD_DTYPE)),
+                        other + (mine, mine_pay), n_missing, extra, n_changed, len(recs), live,
+                        {'lock_wait_seconds': wait, 'lock_hold_seconds': hold})
 
     def records_payload(self):
         raw, pay = self.L.utxo_dump_payload(self.h)
@@ -899,6 +1114,30 @@ class UtxoIndex:
         behind any queued block apply (``grid_blocks`` sizes its launch: a test lever); host backends: a dump
         and 65 compressions per entry on the CPU."""
         return self.be.state_digest(_tag_mask(tags), grid_blocks)
+
+    @_locked
+    def diff_records(self, recs: np.ndarray, pay: Optional[np.ndarray] = None, tags: Optional[Iterable[int]] = None,
+                     *, limit: int = DIFF_LIMIT, chunk_records: int = 0) -> UtxoDiff:
+        """WHERE the index differs from the record set O = (``recs``, ``pay``; ``pay=None``: no payloads): a
+        :class:`UtxoDiff` of the missing, extra and changed entries, an entry being what :meth:`state_digest`
+        hashes, so for O without repeated outpoints the diff is empty exactly when ``state_digest(tags)`` equals
+        ``records_digest`` of O. ``tags`` as in :meth:`state_digest`: O is first cut to the records whose tag is
+        in them and the index to its live entries whose tag is; an outpoint of O that is live under a tag outside
+        them is ``changed``, not missing plus extra. ``limit`` caps each list, the counts stay exact: a truncated
+        ``missing`` or ``changed`` list holds the first ``limit`` such records in O's order, a truncated ``extra``
+        list some ``limit`` of them. ``ValueError``: a record with an index above 255 or a tag above 31, payloads
+        that are not one per record, or an outpoint that O holds more than once and that is live in the index
+        (one that is not live is reported missing once per occurrence). GPU backend: one pass over the HBM table
+        behind any queued block apply (``_GpuBackend.diff``; ``chunk_records`` sizes its uploads: a test lever,
+        ignored by the host backends); host backends: a dump, then ``diff_vectorised`` (``host``) or the
+        reference ``diff_of`` (``host-py``)."""
+        if not isinstance(limit, (int, np.integer)) or limit < 0:
+            raise ValueError('limit is a count >= 0')
+        if not isinstance(chunk_records, (int, np.integer)) or not 0 <= chunk_records < 1 << 32:
+            raise ValueError('chunk_records is a count >= 0 (0: the default)')
+        mask = _tag_mask(tags)
+        recs, pay = _masked(*_diff_arrays(recs, pay), mask)
+        return self.be.diff(recs, pay, mask, min(int(limit), 0xffffffff), int(chunk_records))
 
     @_locked
     def records_payload(self, sort: bool = True):

@@ -22,6 +22,17 @@ stake flag; on a GPU node one pass over the HBM table, ``utxo_state_digest``). O
 replicas, or a replica and a snapshot, hold the same set exactly when their lines agree. With ``--snapshot FILE`` the
 line also carries ``"snapshot_digest"`` (of the file's records and payloads, ``records_digest``) and ``"match"``;
 exit status 1 on a mismatch.
+``python -m upow_amd.tools utxo-diff --snapshot F [--db PATH] [--limit N] [--out FILE]``: WHERE the UTXO index and a
+snapshot file differ (``UtxoIndex.diff_records``; on a GPU node one pass over the HBM table, ``utxo_diff``).
+``utxo-diff --sql [--db PATH] [--limit N] [--out FILE]``: the index against the ledger's own SQL tables, one bulk
+query per table and one diff: the audit that scales. ``utxo-diff --snapshot A --against B``: two snapshot files (A
+loaded into a scratch index). One JSON line per differing entry, to ``--out FILE`` when given: ``{"kind": "missing" |
+"extra" | "changed", "tx_hash", "index", "table", "amount", "address", "is_stake"}``; ``missing`` is in the other set
+and not in the index, ``extra`` the reverse, and a changed entry shows both sides as ``"other": {...}, "index_entry":
+{...}``. Amounts are decimal strings, addresses the raw 33 or 64 bytes as hex; an entry without payload has nulls. At
+most ``--limit`` (default 65536) lines per kind. The last line printed is the summary ``{"equal", "missing", "extra",
+"changed", "compared", "entries", "truncated", "backend", "seconds"}`` with the exact counts. Exit status 1 unless
+the sets are equal.
 ``python -m upow_amd.tools materialise --db <rankN ledger>``: bring a lean cluster follower's SQL tables to its
 tip from its op log (ledger/lean.py); every other command does this first when the ledger has an op log.
 ``python -m upow_amd.tools sign-batch --keys F --digests F --out F [--device gpu|cpu]``: bulk RFC 6979 signing
@@ -136,6 +147,52 @@ async def utxo_digest(path: str = None, snapshot_path: str = None, full: bool = 
     return res
 
 
+def _diff_entry(rec, pay) -> dict:
+    """One side of a diff line: the fields of an entry that the diff compares (no payload: nulls)."""
+    from .ledger.utxo import TABLE_BY_TAG
+    tag, length = int(rec[36]), int(pay['len'])
+    known = length in (33, 64)
+    return {'table': TABLE_BY_TAG.get(tag, str(tag)),
+            'amount': str(Decimal(int(pay['amount'])) / SMALLEST) if known else None,
+            'address': bytes(pay['addr'][:length]).hex() if known else None,
+            'is_stake': bool(int(pay['flags']) & 1) if known else False}
+
+
+async def utxo_diff(path: str = None, snapshot_path: str = None, sql: bool = False, against: str = None,
+                    limit: int = None, db: Database = None):
+    """The ``utxo-diff`` command's lines: (one dict per differing entry: missing, then extra, then changed, each
+    in (tx_hash, index) order; the summary dict). The index (with ``against``: a scratch index loaded from the
+    snapshot ``snapshot_path``) against the other set: the snapshot ``against``, else the ledger's SQL tables
+    (``sql``), else the snapshot ``snapshot_path``."""
+    import time
+
+    from .ledger import snapshot
+    from .ledger.utxo import DIFF_LIMIT, UtxoIndex
+    if against:
+        index = UtxoIndex()
+        index.reset_records(*snapshot.read(snapshot_path)[1:])
+        _, recs, pay = snapshot.read(against)
+    else:
+        db = db or await open_ledger(path)
+        index = db.utxo
+        recs, pay = db._utxo_arrays_from_sql() if sql else snapshot.read(snapshot_path)[1:]
+    t = time.perf_counter()
+    d = index.diff_records(recs, pay, limit=DIFF_LIMIT if limit is None else limit)
+    seconds = time.perf_counter() - t
+    lines = []
+    for kind, (r, p) in (('missing', d.missing), ('extra', d.extra)):
+        for k in range(len(r)):
+            lines.append({'kind': kind, 'tx_hash': bytes(r[k, :32]).hex(), 'index': int(r[k, 32]),
+                          **_diff_entry(r[k], p[k])})
+    ro, po, ri, pi = d.changed
+    for k in range(len(ro)):
+        lines.append({'kind': 'changed', 'tx_hash': bytes(ro[k, :32]).hex(), 'index': int(ro[k, 32]),
+                      'other': _diff_entry(ro[k], po[k]), 'index_entry': _diff_entry(ri[k], pi[k])})
+    return lines, {'equal': d.equal, 'missing': d.n_missing, 'extra': d.n_extra, 'changed': d.n_changed,
+                   'compared': d.compared, 'entries': d.entries, 'truncated': d.truncated,
+                   'backend': index.backend_name, 'seconds': round(seconds, 6)}
+
+
 async def rebuild_utxo(path: str = None):
     db = await open_ledger(path)
     outputs = await db.get_unspent_outputs_from_all_transactions()
@@ -193,7 +250,8 @@ def vanity_keys(prefix: str, ignore_case: bool = False, count: int = 1, max_keys
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('command', choices=['rebuild-utxo', 'utxo-hash', 'snapshot', 'verify-utxo', 'address-utxos',
-                                        'holders', 'materialise', 'sign-batch', 'vanity', 'utxo-digest'])
+                                        'holders', 'materialise', 'sign-batch', 'vanity', 'utxo-digest',
+                                        'utxo-diff'])
     ap.add_argument('address', nargs='*')
     ap.add_argument('--db', default=None)
     ap.add_argument('--out', default=None)
@@ -207,6 +265,9 @@ def main(argv=None):
     ap.add_argument('--max-keys', type=int, default=None)
     ap.add_argument('--snapshot', default=None)
     ap.add_argument('--full', action='store_true')
+    ap.add_argument('--sql', action='store_true')
+    ap.add_argument('--against', default=None)
+    ap.add_argument('--limit', type=int, default=None)
     a = ap.parse_args(argv)
     if a.command == 'sign-batch':
         if not (a.keys and a.digests and a.out):
@@ -258,6 +319,24 @@ def main(argv=None):
             raise SystemExit(f'utxo-digest: {e}')
         print(json.dumps(res))
         return 0 if res.get('match', True) else 1
+    elif a.command == 'utxo-diff':
+        if bool(a.snapshot) == a.sql or (a.against and not a.snapshot):
+            ap.error('utxo-diff needs --snapshot FILE (with --against FILE for two files) or --sql')
+        if a.limit is not None and a.limit < 0:
+            ap.error('--limit is a count >= 0')
+        try:
+            lines, summary = asyncio.run(utxo_diff(a.db, a.snapshot, a.sql, a.against, a.limit))
+        except (ValueError, OSError) as e:
+            raise SystemExit(f'utxo-diff: {e}')
+        out = open(a.out, 'w') if a.out else sys.stdout
+        try:
+            for line in lines:  # one JSON line per differing entry
+                print(json.dumps(line), file=out)
+        finally:
+            if a.out:
+                out.close()
+        print(json.dumps(summary))
+        return 0 if summary['equal'] else 1
     elif a.command == 'rebuild-utxo':
         asyncio.run(rebuild_utxo(a.db))
     elif a.command in ('snapshot', 'verify-utxo'):
