@@ -155,6 +155,30 @@ PYBIND11_MODULE(_native, m) {
           py::arg("header"), py::arg("v"), py::arg("variant"),
           "pow_job_h0 through the device function of one kernel variant (host arithmetic)");
 
+    m.def("pow_split_consts", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl) {
+        const PowSplitConsts c = pow_split_consts(make_job(header, tmask, tword, fs, fl));
+        return py::dict(py::arg("ca") = c.ca, py::arg("ce") = c.ce, py::arg("c17") = c.c17, py::arg("c24") = c.c24,
+                        py::arg("mid0") = c.mid0, py::arg("range_ok") = c.range_ok,
+                        py::arg("range_base") = c.range_base, py::arg("range_width") = c.range_width,
+                        py::arg("min_log2") = c.min_log2, py::arg("max_log2") = c.max_log2);
+    }, py::arg("header"), py::arg("tmask"), py::arg("tword"), py::arg("frac_shift"), py::arg("frac_limit"),
+       "job constants of kernel variant 10 (108-byte header): a11 = ca + v, e11 = ce + v, W17 = c17 + v, "
+       "W24 = c24 + v; the range form of the hit predicate, or range_ok False where the job keeps the mask form");
+
+    m.def("pow_range_hit", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
+                              uint32_t h0) { return pow_range_hit_host(make_job(header, tmask, tword, fs, fl), h0); },
+          py::arg("header"), py::arg("tmask"), py::arg("tword"), py::arg("frac_shift"), py::arg("frac_limit"),
+          py::arg("h0"), "variant 10's one-compare hit predicate on a digest word H0 (range_ok jobs only)");
+
+    m.def("pow_split_wave", [](py::bytes header, uint32_t vb, uint32_t p, uint32_t u_first, uint32_t iters) {
+        const std::vector<uint32_t> h = pow_split_wave_host(make_job(header, 0, 0, 0, 16), vb, p, u_first, iters);
+        py::array_t<uint32_t> out({py::ssize_t(iters), py::ssize_t(64)});
+        std::memcpy(out.mutable_data(), h.data(), h.size() * sizeof(uint32_t));
+        return out;
+    }, py::arg("header"), py::arg("vb"), py::arg("p"), py::arg("u_first"), py::arg("iters"),
+       "variant 10's wave loop on the host: H0[iteration][lane] for nonce words vb + U + (lane << p), "
+       "U = u_first .. u_first + iters - 1, with the kernel's cached lane constants");
+
     m.def("pow_search_host", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
                                 uint64_t start, uint64_t count, int threads) {
         PowJobHost j = make_job(header, tmask, tword, fs, fl);

@@ -29,6 +29,23 @@ int pow_variant_count();  // kernel variants are numbered 0 (the default) .. pow
 uint32_t pow_job_h0_host(const PowJobHost& job, uint32_t v);
 uint32_t pow_job_h0_host(const PowJobHost& job, uint32_t v, int variant);  // through variant's device function
 
+// Kernel variant 10 (the lane/uniform split of the 108-byte search, csrc/pow_search.hip): the job constants it
+// adds, for the tests. A piece of the search is v = vb + U + (lane << p), U in [0, 2^p) uniform across a wave.
+struct PowSplitConsts {
+    uint32_t ca = 0, ce = 0, c17 = 0, c24 = 0;  // a11 = ca + v, e11 = ce + v, W17 = c17 + v, W24 = c24 + v
+    uint32_t mid0 = 0;                          // H0 = mid0 + a64
+    bool range_ok = false;                      // the hit predicate is (H0 - tword) < range_width, unsigned
+    uint32_t range_base = 0, range_width = 0;   // range_base = mid0 - tword
+    int min_log2 = 0, max_log2 = 0;             // the p of the smallest and the largest piece pow_search_gpu cuts
+};
+PowSplitConsts pow_split_consts(const PowJobHost& job);
+// The kernel's range form of the hit predicate on a given H0 (range_ok jobs only)
+bool pow_range_hit_host(const PowJobHost& job, uint32_t h0);
+// The wave loop of variant 10 on the host: 64 lanes with cached lane constants that are recomputed when a carry
+// flips, U = u_first .. u_first + iters - 1. Returns H0 of every lane per iteration, [iteration][lane].
+std::vector<uint32_t> pow_split_wave_host(const PowJobHost& job, uint32_t vb, uint32_t p, uint32_t u_first,
+                                          uint32_t iters);
+
 bool pow_check_word_host(const PowJobHost& job, uint32_t v);
 PowResult pow_search_host(const PowJobHost& job, uint64_t start, uint64_t count, int threads);
 PowResult pow_search_gpu(const PowJobHost& job, uint64_t start, uint64_t count, int grid_blocks,

@@ -4,7 +4,8 @@
 // miner.py:43-61 / upow/manager.py:130-151.
 //
 // MI355X design
-//  * one nonce per lane, 64 nonces per wavefront, grid-strided over the 2^32 nonce space;
+//  * one nonce per lane, 64 nonces per wavefront, grid-strided over the 2^32 nonce space (variant 10: a wave
+//    walks U with its lanes 2^p words apart, a range cut into power-of-two pieces);
 //  * the header's first 64-byte block is nonce independent -> host midstate;
 //  * v2 header (108 B): the tail block's words W0..W9 are nonce independent too, so the host also
 //    runs rounds 0..9 and the kernel starts at round 10 (W10 = the nonce word);
@@ -21,11 +22,16 @@
 //  * rotates lower to v_alignbit_b32, the 3-input XORs of the Sigma functions and Maj to the gfx950
 //    v_bitop3_b32 (truth tables 0x96 / 0xE8), 3-input adds to v_add3_u32 (1107 VALU ops per nonce in
 //    the v2 loop body vs 1359 with 2-input XORs);
-//  * the default v2 kernel (pow_h0_sched, variant 9) issues pow_h0_pre's instructions in a pinned order with an
-//    s_sleep 0 in front of every v_alignbit_b32 and v_add3_u32: behind that sequencer-only instruction the two
-//    slow opcodes cost about a cycle less (3.66 against 3.94 cycles per VALU instruction, docs/PERF.md);
+//  * variant 9 (pow_h0_sched) issues pow_h0_pre's instructions in a pinned order with an s_sleep 0 in front of
+//    every v_alignbit_b32 and v_add3_u32: behind that sequencer-only instruction the two slow opcodes cost about
+//    a cycle less (3.66 against 3.94 cycles per VALU instruction, docs/PERF.md);
+//  * the default v2 kernel (pow_a_split, variant 10) is variant 9 with the lane index in the TOP bits of the nonce
+//    word, v = vb + U + (lane << p): what all 64 lanes of a wave would compute alike (the low p bits of W10, a11,
+//    e11, W17, W24 and their sigmas, round 11's Ch and Maj) is done once per wave on the SALU, one scalar
+//    instruction in the place of one s_sleep 0, and the per-lane high bits are loop-invariant VGPRs: 1,085 VALU
+//    instructions per nonce against 1,108, 446 rotates against 462 (docs/PERF.md, "PoW lane/uniform split");
 //  * the predicate only needs digest word H0 for difficulty < 8 (8 hex nibbles) -> one compare per
-//    nonce; hits are appended with an atomic to a small candidate list and re-checked exactly on the
+//    nonce (variant 10: one add and one unsigned compare, (H0 - tword) < width); hits are appended with an atomic to a small candidate list and re-checked exactly on the
 //    host (covers d >= 8 and the d < 1 "whole hash" quirk).
 #include <hip/hip_runtime.h>
 
@@ -54,6 +60,13 @@ struct PowJobDev {
     uint32_t ca, ce;   // round R0 with a constant state: a' = ca + W[R0], e' = ce + W[R0]
     uint32_t hk[3];    // rounds R0+1..R0+3, whose h is still constant: h + K[i] (+ W[i] where W[i] is constant)
     uint32_t kw[64];   // W[i] constant: K[i] + W[i]; W[i] partly constant (i >= 16): the sum of its constant terms
+    // Variant 10 (pow_h0_split, 108-byte header). W17 = kw[17] + v already; the rest of what it adds:
+    uint32_t c24;      // W24 = c24 + v (kw[24] + kw[17])
+    uint32_t he;       // round R0+1: e' = he + Sigma1(e) + Ch(e, f, g), he = st[2] + hk[0]
+    uint32_t fxg, bxc; // round R0+1: Ch(e, f, g) = g ^ (e & fxg), Maj(a, b, c) = (b & c) ^ (a & bxc)
+    // the hit predicate as one range check, (H0 - tword) < range_width unsigned, with H0 = mid[0] + a:
+    // a + range_base < range_width. range_ok = 0: the mask is no prefix or the width no 32-bit number.
+    uint32_t range_ok, range_base, range_width;
 };
 
 // Which words of the tail block's message schedule depend on the nonce (vec) and, of those, which also have
@@ -212,7 +225,14 @@ struct PowSchedRegs {
     uint32_t w[16];  // the rolling window; only nonce-dependent words ever live here
     uint32_t s[8];   // a..h, rotating: in round i, a = s[-i & 7] .. h = s[(7 - i) & 7]
     uint32_t t[4], u[4], q[3];  // temporaries of the schedule word, the Sigma1/Ch path and the Sigma0/Maj path
+    // SPLIT (variant 10) only: the sigmas of W10, W17 and W24 in two halves, wave-uniform low bits (xs, SGPRs) and
+    // per-lane high bits (xl, VGPRs that do not change from iteration to iteration); sigma = xs ^ xl.
+    //  0 sigma0(W10)   1 sigma1(W17)   2 sigma0(W17)   3 sigma1(W24)   4 sigma0(W24)
+    uint32_t xs[5], xl[5];
 };
+// Index into xs / xl of sigma0(W[j-15]) and of sigma1(W[j-2]), or -1 where the word is not split
+constexpr int pow_split_s0(int j) { return j - 15 == 10 ? 0 : j - 15 == 17 ? 2 : j - 15 == 24 ? 4 : -1; }
+constexpr int pow_split_s1(int j) { return j - 2 == 17 ? 1 : j - 2 == 24 ? 3 : -1; }
 // What one instruction is pinned by: its VGPR inputs and its result (all null: the instruction does not exist)
 struct PowOpRegs {
     uint32_t* in[3] = {nullptr, nullptr, nullptr};
@@ -224,21 +244,22 @@ struct PowOpRegs {
 
 // Instruction k (0..9) of schedule word W[j]; instructions of terms that are nonce independent do not exist.
 //  0-3 sigma0(W[j-15]) -> t[0]    4-7 sigma1(W[j-2]) -> t[1]    8 the first add of a four-term sum    9 W[j]
-constexpr bool pow_sched_op_exists(const PowWordKinds& kinds, int j, int k) {
+// split: a split word's sigma is one XOR, xs ^ xl, in the place of the XOR3 (k = 3 / 7); its rotates and shift go
+constexpr bool pow_sched_op_exists(const PowWordKinds& kinds, int j, int k, bool split = false) {
     if (j < 16 || j > 63 || !kinds.vec[j]) return false;
-    if (k < 4) return kinds.vec[j - 15];
-    if (k < 8) return kinds.vec[j - 2];
+    if (k < 4) return kinds.vec[j - 15] && !(split && pow_split_s0(j) >= 0 && k < 3);
+    if (k < 8) return kinds.vec[j - 2] && !(split && pow_split_s1(j) >= 0 && k < 7);
     const int n = int(kinds.has_const[j]) + int(kinds.vec[j - 16]) + int(kinds.vec[j - 15]) + int(kinds.vec[j - 7]) +
                   int(kinds.vec[j - 2]);
     return k == 9 || n == 4;
 }
 
 // RUN: execute the instruction; otherwise only name its registers
-template <int LAYOUT, int J, int K, bool RUN>
+template <int LAYOUT, int J, int K, bool RUN, bool SPLIT = false>
 __host__ __device__ __forceinline__ PowOpRegs pow_sched_op(const PowJobDev& job, PowSchedRegs& r) {
     constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
     PowOpRegs o;
-    if constexpr (pow_sched_op_exists(kinds, J, K)) {
+    if constexpr (pow_sched_op_exists(kinds, J, K, SPLIT)) {
         constexpr int j = J, k = K;
         constexpr bool c = kinds.has_const[j], v16 = kinds.vec[j - 16], v15 = kinds.vec[j - 15],
                        v7 = kinds.vec[j - 7], v2 = kinds.vec[j - 2];
@@ -246,7 +267,14 @@ __host__ __device__ __forceinline__ PowOpRegs pow_sched_op(const PowJobDev& job,
         uint32_t(&t)[4] = r.t;
         uint32_t& x15 = w[(j - 15) & 15];
         uint32_t& x2 = w[(j - 2) & 15];
-        if constexpr (k < 4) {
+        // a split sigma reads an SGPR and a VGPR that lives across iterations: neither is pinned (as w[10] is not)
+        if constexpr (k < 4 && SPLIT && pow_split_s0(j) >= 0) {
+            o = {{nullptr, nullptr, nullptr}, &t[0]};
+            if (RUN) t[0] = r.xs[pow_split_s0(j)] ^ r.xl[pow_split_s0(j)];
+        } else if constexpr (k >= 4 && k < 8 && SPLIT && pow_split_s1(j) >= 0) {
+            o = {{nullptr, nullptr, nullptr}, &t[1]};
+            if (RUN) t[1] = r.xs[pow_split_s1(j)] ^ r.xl[pow_split_s1(j)];
+        } else if constexpr (k < 4) {
             if (k == 3) o = {{&t[2], &t[1], &t[0]}, &t[0]};
             else o = {{&x15, nullptr, nullptr}, &t[k]};
             if (RUN) *o.out = k == 0 ? P_ROTR(x15, 7) : k == 1 ? P_ROTR(x15, 18) : k == 2 ? x15 >> 3 : P_XOR3(t[0], t[1], t[2]);
@@ -354,7 +382,7 @@ __host__ __device__ __forceinline__ void pow_static_for(F&& f) {
     pow_static_for<B>(f, std::make_integer_sequence<int, (E > B ? E - B : 0)>{});
 }
 
-template <int LAYOUT, int D, bool TWO_PATH>
+template <int LAYOUT, int D, bool TWO_PATH, bool SPLIT = false>
 struct PowOrder {
     static constexpr int R0 = 10, FIRST = R0 + 4;  // first round whose whole state is nonce dependent
     static constexpr int SLOTS = 24, STEPS = (64 - FIRST) * SLOTS;
@@ -373,7 +401,7 @@ struct PowOrder {
     }
     static constexpr bool exists(int g) {
         if (g < 0 || g >= STEPS) return false;
-        if (is_sched(g)) return pow_sched_op_exists(pow_word_kinds(LAYOUT), round_of(g) + D, sched_k(g));
+        if (is_sched(g)) return pow_sched_op_exists(pow_word_kinds(LAYOUT), round_of(g) + D, sched_k(g), SPLIT);
         return !(round_op(g) == R_E && round_of(g) == 63);
     }
     // v_alignbit_b32 and v_add3_u32 issue at 4.1 cycles, everything else here at 2.3 (docs/PERF.md)
@@ -400,6 +428,18 @@ struct PowOrder {
     // FILL: an s_sleep 0, which does nothing and is no VALU instruction, goes in front of step g
     //  1 if g is a rotate    2 if g is slow (a rotate or an add3)
     static constexpr bool fill_before(int fill, int g) { return fill == 1 ? rotate(g) : fill == 2 ? slow(g) : false; }
+    // Variant 10 puts one scalar instruction of its wave-uniform work into a filler's place: the first kUopsPerRound
+    // fillers of a round (every round has its six rotates and two add3) are numbered on through the rounds. The
+    // number of the filler in front of step g, or -1. The first step of all has no filler in front of it.
+    static constexpr int kUopsPerRound = 8;
+    static constexpr int uop_index(int fill, int g) {
+        if (g < 0 || !fill_before(fill, g)) return -1;
+        const int first = exists(0) ? 0 : next(0), begin = (g / SLOTS) * SLOTS;
+        int local = 0;
+        for (int h = begin; h < g; ++h)
+            if (h != first && fill_before(fill, h)) ++local;
+        return g != first && local < kUopsPerRound ? (g / SLOTS) * kUopsPerRound + local : -1;
+    }
     static constexpr int next(int g) {  // the next step that has an instruction, or -1
         if (g < 0) return -1;
         for (int n = g + 1; n < STEPS; ++n)
@@ -409,10 +449,21 @@ struct PowOrder {
     template <int G, bool RUN>
     static __host__ __device__ __forceinline__ PowOpRegs op(const PowJobDev& job, PowSchedRegs& r) {
         if constexpr (!exists(G)) return {};
-        else if constexpr (is_sched(G)) return pow_sched_op<LAYOUT, round_of(G) + D, sched_k(G), RUN>(job, r);
+        else if constexpr (is_sched(G)) return pow_sched_op<LAYOUT, round_of(G) + D, sched_k(G), RUN, SPLIT>(job, r);
         else return pow_round_op<LAYOUT, round_of(G), round_op(G), RUN>(job, r);
     }
 };
+
+template <int LAYOUT, int FROM, int TO>
+__host__ __device__ __forceinline__ void pow_sched_open_rounds(const PowJobDev& job, PowSchedRegs& r);
+// The scalar program of a pinned loop: uop<N> is one SALU instruction that goes into filler N's place
+struct PowNoScalar {
+    static constexpr int kCount = 0;
+    template <int N>
+    __host__ __device__ __forceinline__ void uop(const PowJobDev&, PowSchedRegs&) {}
+};
+template <class O, int FILL, class S>
+__host__ __device__ __forceinline__ void pow_sched_pinned(const PowJobDev& job, PowSchedRegs& r, S& sc);
 
 template <int LAYOUT, int D, bool TWO_PATH, int FILL>
 __host__ __device__ __forceinline__ uint32_t pow_h0_sched(const PowJobDev& job, uint32_t v) {
@@ -420,7 +471,6 @@ __host__ __device__ __forceinline__ uint32_t pow_h0_sched(const PowJobDev& job, 
     static_assert(D >= 0 && D < 16, "W[i+D] takes the place of W[i+D-16], which round i must not need any more");
     using O = PowOrder<LAYOUT, D, TWO_PATH>;
     constexpr int R0 = O::R0, FIRST = O::FIRST;
-    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
     PowSchedRegs r = {};
     r.w[10] = v;
     {
@@ -432,6 +482,7 @@ __host__ __device__ __forceinline__ uint32_t pow_h0_sched(const PowJobDev& job, 
     pow_static_for<16, FIRST + D>([&](auto j) {
         pow_static_for<0, 10>([&](auto k) { pow_sched_op<LAYOUT, decltype(j)::value, decltype(k)::value, true>(job, r); });
     });
+    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
 #pragma unroll
     for (int i = R0 + 1; i < FIRST; ++i) {
         uint32_t(&s)[8] = r.s;
@@ -446,12 +497,46 @@ __host__ __device__ __forceinline__ uint32_t pow_h0_sched(const PowJobDev& job, 
         d = d + t1;
         h = t1 + t2;
     }
+    PowNoScalar none;
+    pow_sched_pinned<O, FILL>(job, r, none);
+    return job.mid[0] + r.s[(0 - 64) & 7];
+}
+
+// Rounds FROM..TO-1 of the rounds whose state is still partly uniform, in the compiler's order: the loop of
+// pow_h0_sched for variant 10. (pow_h0_sched keeps its own copy: called through this function the compiler orders
+// variant 6-9's rounds 11..13 differently, and those kernels are kept instruction for instruction.)
+template <int LAYOUT, int FROM, int TO>
+__host__ __device__ __forceinline__ void pow_sched_open_rounds(const PowJobDev& job, PowSchedRegs& r) {
+    constexpr int R0 = 10;
+    constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
+#pragma unroll
+    for (int i = FROM; i < TO; ++i) {
+        uint32_t(&s)[8] = r.s;
+        uint32_t &a = s[(0 - i) & 7], &b = s[(1 - i) & 7], &c = s[(2 - i) & 7], &d = s[(3 - i) & 7];
+        uint32_t &e = s[(4 - i) & 7], &f = s[(5 - i) & 7], &g = s[(6 - i) & 7], &h = s[(7 - i) & 7];
+        const uint32_t x = kinds.vec[i] ? job.hk[i - R0 - 1] + r.w[i & 15] : job.hk[i - R0 - 1];
+        uint32_t t1 = x + P_BSIG1(e) + P_CH(e, f, g);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(t1));  // one add3 here, then e and a from it, as in pow_h0_pre
+#endif
+        const uint32_t t2 = P_BSIG0(a) + P_MAJ(a, b, c);
+        d = d + t1;
+        h = t1 + t2;
+    }
+}
+
+// The pinned part: every step of order O from round O::FIRST on, FILL as above. Where the scalar program sc has
+// an instruction for a filler's place it goes there and the s_sleep 0 does not: a scalar instruction in front of a
+// slow one does what the filler does (docs/PERF.md, "PoW lane/uniform split").
+template <class O, int FILL, class S>
+__host__ __device__ __forceinline__ void pow_sched_pinned(const PowJobDev& job, PowSchedRegs& r, S& sc) {
     pow_static_for<0, O::STEPS>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         if constexpr (O::exists(g)) {
             const PowOpRegs me = O::template op<g, true>(job, r);
-#if defined(__HIP_DEVICE_COMPILE__)
             constexpr int g1 = O::next(g), g2 = O::next(g1);
+            constexpr int uop = S::kCount > 0 ? O::uop_index(FILL, g1) : -1;
+#if defined(__HIP_DEVICE_COMPILE__)
             const PowOpRegs n1 = O::template op<g1, false>(job, r), n2 = O::template op<g2, false>(job, r);
             // An asm result must not be read by the very next instruction (s_nop), and the nonce word is live
             // across iterations (redefining it would cost a copy). Redefining this instruction's own result as
@@ -465,16 +550,232 @@ __host__ __device__ __forceinline__ uint32_t pow_h0_sched(const PowJobDev& job, 
             else asm volatile("" ::"v"(*me.out));
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (O::fill_before(FILL, g1)) {
-                __builtin_amdgcn_s_sleep(0);
+                if constexpr (uop >= 0 && uop < S::kCount) sc.template uop<uop>(job, r);
+                else __builtin_amdgcn_s_sleep(0);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #else
             (void)me;
+            (void)g2;
+            if constexpr (uop >= 0 && uop < S::kCount) sc.template uop<uop>(job, r);
 #endif
         }
     });
-    return job.mid[0] + r.s[(0 - 64) & 7];
 }
+
+// Variant 10: the lane index in the nonce word's top bits, wave-uniform work on the SALU.
+// A piece of the search is v = vb + U + (lane << p), U in [0, 2^p) the same for all 64 lanes of a wave. The
+// nonce word enters the tail block additively five times: W10 = v itself, a11 = ca + v, e11 = ce + v,
+// W17 = kw[17] + v and W24 = c24 + v. Each is x = s + (lane << p) with a wave-uniform s = c + vb + U, so
+//   x = lo | hi,   lo = s & (2^p - 1) wave-uniform,   hi = ((s >> p) + lane) << p,
+// and hi changes only when s >> p does, once per piece as U grows (the carry out of bit p-1). The sigmas are
+// GF(2)-linear and Ch / Maj with uniform second and third operands bitwise, and lo and hi have no bit in common:
+//   sigma(x) = sigma(lo) ^ sigma(hi),   Ch(x, f, g) = (Ch(lo, f, g) & (2^p - 1)) + (Ch(hi, f, g) & ~(2^p - 1)).
+// The lo halves are plain C++ on uniform values (SALU); the hi halves are per-lane constants in VGPRs, recomputed
+// in a wave-uniform branch when their s >> p differs from the cached one. That takes the rotates of
+// sigma0(W10), sigma0/1(W17), sigma0/1(W24) and of round 11 out of the loop; every other instruction is
+// variant 9's, in its order and with its fillers.
+struct PowSplitKeys { uint32_t v, e, a, w17, w24; };  // the five sums, or their s >> p
+struct PowSplitLane {
+    uint32_t lanep;           // lane << p
+    uint32_t xl[5];           // PowSchedRegs::xl
+    uint32_t s1, ch, s0, cm;  // round 11: Sigma1(e_hi), Ch(e_hi, f, g), Sigma0(a_hi), Ch(e_hi, f, g) + Maj(a_hi, b, c)
+};
+// Rotates of a wave-uniform value x on the SALU, which has no rotate: x twice in an SGPR pair, and a 64-bit right
+// shift by n leaves rotr(x, n) in the low word.
+#define U_PAIR(x) ((uint64_t(x) << 32) | (x))
+#define U_ROTR(xx, n) uint32_t((xx) >> (n))
+__host__ __device__ __forceinline__ uint32_t pow_u_bsig0(uint32_t x) { const uint64_t xx = U_PAIR(x); return U_ROTR(xx, 2) ^ U_ROTR(xx, 13) ^ U_ROTR(xx, 22); }
+__host__ __device__ __forceinline__ uint32_t pow_u_bsig1(uint32_t x) { const uint64_t xx = U_PAIR(x); return U_ROTR(xx, 6) ^ U_ROTR(xx, 11) ^ U_ROTR(xx, 25); }
+
+// The wave-uniform program, one SALU instruction per step (uop<N>), each in the place of one filler of the pinned
+// loop (PowOrder::uop_index). Steps 0..32 make this iteration's xs (the first is needed in round 17, the steps
+// run in rounds 14..18); steps 33..56 make round 11's scalars of the NEXT iteration, sv + 1, which the top of the
+// loop then only reads. On the device every step sits between two empty asm statements that redefine the
+// program's registers: they hold the step's place among the pinned instructions, keep the values in SGPRs and
+// hide from the compiler that a shift pair is a rotate, which it would select as v_alignbit_b32, back on the VALU.
+struct PowSplitScalar {
+    static constexpr int kCount = 57;
+    uint32_t sv;             // this iteration's vb + U
+    uint32_t m, glo, bclo;   // 2^p - 1, g & m, b & c & m (round 11's g, b, c)
+    uint32_t x1, x0, se, sa; // round 11: Sigma1(e_lo), Sigma0(a_lo), he + Ch_lo, hk[0] + Ch_lo + Maj_lo
+    uint32_t a, b, t, l;     // temporaries
+    uint64_t pp;
+
+    // Round 11's scalars for the word sum at `at`, all at once (the prologue; the steps below do the same)
+    __host__ __device__ __forceinline__ void round11(const PowJobDev& job, uint32_t at) {
+        const uint32_t elo = (at + job.ce) & m, alo = (at + job.ca) & m;
+        const uint32_t chlo = (elo & job.fxg) ^ glo, mjlo = (alo & job.bxc) ^ bclo;
+        x1 = pow_u_bsig1(elo);
+        x0 = pow_u_bsig0(alo);
+        se = chlo + job.he;
+        sa = chlo + mjlo + job.hk[0];
+    }
+
+    template <int N>
+    __host__ __device__ __forceinline__ void uop(const PowJobDev& job, PowSchedRegs& r) {
+        static_assert(N >= 0 && N < kCount, "no such step");
+        uint32_t(&xs)[5] = r.xs;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(a), "+s"(b), "+s"(t), "+s"(l), "+s"(pp), "+s"(sv));
+#endif
+        // sigma1, sigma0 of the pair pp / the word l into xs[K1], xs[K0]: ten steps from FIRST on
+#define U_SIG1(FIRST, K1)                                                                                      \
+        else if constexpr (N == FIRST) a = U_ROTR(pp, 17); else if constexpr (N == FIRST + 1) b = U_ROTR(pp, 19); \
+        else if constexpr (N == FIRST + 2) a ^= b; else if constexpr (N == FIRST + 3) b = l >> 10;                \
+        else if constexpr (N == FIRST + 4) xs[K1] = a ^ b;
+#define U_SIG0(FIRST, K0)                                                                                      \
+        else if constexpr (N == FIRST) a = U_ROTR(pp, 7); else if constexpr (N == FIRST + 1) b = U_ROTR(pp, 18); \
+        else if constexpr (N == FIRST + 2) a ^= b; else if constexpr (N == FIRST + 3) b = l >> 3;                \
+        else if constexpr (N == FIRST + 4) xs[K0] = a ^ b;
+        if constexpr (N == 0) l = sv + job.kw[17];
+        else if constexpr (N == 1) l &= m;
+        else if constexpr (N == 2) pp = U_PAIR(l);
+        U_SIG1(3, 1)
+        U_SIG0(8, 2)
+        else if constexpr (N == 13) l = sv & m;
+        else if constexpr (N == 14) pp = U_PAIR(l);
+        U_SIG0(15, 0)
+        else if constexpr (N == 20) l = sv + job.c24;
+        else if constexpr (N == 21) l &= m;
+        else if constexpr (N == 22) pp = U_PAIR(l);
+        U_SIG1(23, 3)
+        U_SIG0(28, 4)
+        // the next iteration's round 11
+        else if constexpr (N == 33) t = sv + 1u;
+        else if constexpr (N == 34) l = t + job.ce;
+        else if constexpr (N == 35) l &= m;
+        else if constexpr (N == 36) pp = U_PAIR(l);
+        else if constexpr (N == 37) a = U_ROTR(pp, 6);
+        else if constexpr (N == 38) b = U_ROTR(pp, 11);
+        else if constexpr (N == 39) a ^= b;
+        else if constexpr (N == 40) b = U_ROTR(pp, 25);
+        else if constexpr (N == 41) x1 = a ^ b;
+        else if constexpr (N == 42) a = l & job.fxg;
+        else if constexpr (N == 43) a ^= glo;  // Ch_lo
+        else if constexpr (N == 44) se = a + job.he;
+        else if constexpr (N == 45) l = t + job.ca;
+        else if constexpr (N == 46) l &= m;
+        else if constexpr (N == 47) pp = U_PAIR(l);
+        else if constexpr (N == 48) b = U_ROTR(pp, 2);
+        else if constexpr (N == 49) t = U_ROTR(pp, 13);
+        else if constexpr (N == 50) b ^= t;
+        else if constexpr (N == 51) t = U_ROTR(pp, 22);
+        else if constexpr (N == 52) x0 = b ^ t;
+        else if constexpr (N == 53) b = l & job.bxc;
+        else if constexpr (N == 54) b ^= bclo;  // Maj_lo
+        else if constexpr (N == 55) a += b;
+        else if constexpr (N == 56) sa = a + job.hk[0];
+#undef U_SIG1
+#undef U_SIG0
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(a), "+s"(b), "+s"(t), "+s"(l), "+s"(pp), "+s"(x1), "+s"(x0), "+s"(se), "+s"(sa),
+                          "+s"(xs[0]), "+s"(xs[1]), "+s"(xs[2]), "+s"(xs[3]), "+s"(xs[4]));
+#endif
+    }
+};
+struct PowSplitCache {
+    PowSplitKeys key;   // s >> p of the five sums, which the lane constants were computed from
+    uint32_t next;      // the first vb + U at which one of them is another
+    PowSplitScalar sc;  // the scalar program's registers; x1, x0, se, sa are those of the coming iteration
+};
+
+// sv = vb + U
+__host__ __device__ __forceinline__ PowSplitKeys pow_split_sums(const PowJobDev& job, uint32_t sv) {
+    return {sv, job.ce + sv, job.ca + sv, job.kw[17] + sv, job.c24 + sv};
+}
+
+// At sv: the lane constants whose key differs from the cached one (all: every one, for the prologue), and the next
+// sv at which a key changes. A sum's s >> p changes when its low p bits wrap, so the first of the five to do so is
+// the one with the largest low part: 2^p minus that many steps from here.
+__host__ __device__ __forceinline__ void pow_split_lane_update(const PowJobDev& job, uint32_t p, uint32_t sv, uint32_t lane,
+                                                               PowSplitCache& cached, PowSplitLane& lc, bool all) {
+    const uint32_t m = (1u << p) - 1u, hm = ~m;
+    const PowSplitKeys s = pow_split_sums(job, sv);
+    const PowSplitKeys key = {s.v >> p, s.e >> p, s.a >> p, s.w17 >> p, s.w24 >> p};
+    if (all || key.v != cached.key.v) {
+        const uint32_t x = (key.v + lane) << p;
+        lc.xl[0] = P_SSIG0(x);
+    }
+    if (all || key.w17 != cached.key.w17) {
+        const uint32_t x = (key.w17 + lane) << p;
+        lc.xl[1] = P_SSIG1(x);
+        lc.xl[2] = P_SSIG0(x);
+    }
+    if (all || key.w24 != cached.key.w24) {
+        const uint32_t x = (key.w24 + lane) << p;
+        lc.xl[3] = P_SSIG1(x);
+        lc.xl[4] = P_SSIG0(x);
+    }
+    if (all || key.e != cached.key.e || key.a != cached.key.a) {
+        const uint32_t eh = (key.e + lane) << p, ah = (key.a + lane) << p;
+        lc.s1 = P_BSIG1(eh);
+        lc.ch = CH(eh, job.st[4], job.st[5]) & hm;
+        lc.s0 = P_BSIG0(ah);
+        lc.cm = lc.ch + (P_MAJ(ah, job.st[0], job.st[1]) & hm);
+    }
+    cached.key = key;
+    uint32_t top = s.v & m;
+    top = (s.e & m) > top ? (s.e & m) : top;
+    top = (s.a & m) > top ? (s.a & m) : top;
+    top = (s.w17 & m) > top ? (s.w17 & m) : top;
+    top = (s.w24 & m) > top ? (s.w24 & m) : top;
+    cached.next = sv + (m - top) + 1u;
+}
+
+// Before a wave's first iteration, whose sv is vb + U
+__host__ __device__ __forceinline__ void pow_split_prologue(const PowJobDev& job, uint32_t p, uint32_t sv, uint32_t lane,
+                                                            PowSplitCache& cached, PowSplitLane& lc) {
+    lc.lanep = lane << p;
+    pow_split_lane_update(job, p, sv, lane, cached, lc, true);
+    PowSplitScalar& sc = cached.sc;
+    sc = {};
+    sc.m = (1u << p) - 1u;
+    sc.glo = job.st[5] & sc.m;
+    sc.bclo = job.st[0] & job.st[1] & sc.m;
+    sc.round11(job, sv);
+}
+
+// a after round 63 (H0 = mid[0] + a) for the lane's nonce word sv + (lane << p); p <= 26. sv goes up by one from
+// call to call after the prologue: the keys can only change at cached.next, and round 11's scalars for this sv
+// were made during the call before.
+template <int FILL>
+__host__ __device__ __forceinline__ uint32_t pow_a_split(const PowJobDev& job, uint32_t p, uint32_t sv, uint32_t lane,
+                                                         PowSplitCache& cached, PowSplitLane& lc) {
+    using O = PowOrder<2, 2, false, true>;
+    static_assert(PowSplitScalar::kCount <= (64 - O::FIRST) * O::kUopsPerRound, "a filler's place for every step");
+    if (sv == cached.next) pow_split_lane_update(job, p, sv, lane, cached, lc, false);
+    PowSplitScalar& sc = cached.sc;
+    sc.sv = sv;
+    PowSchedRegs r = {};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) r.xl[k] = lc.xl[k];
+    const uint32_t v = sv + lc.lanep;
+    r.w[10] = v;
+    {
+        // round 11 from the halves; b, c, f, g are still job constants
+        const uint32_t x1 = sc.x1 ^ lc.s1, x0 = sc.x0 ^ lc.s0;
+        uint32_t(&s)[8] = r.s;
+        constexpr int i = O::R0 + 1;
+        s[(0 - i) & 7] = job.ca + v; s[(1 - i) & 7] = job.st[0]; s[(2 - i) & 7] = job.st[1];
+        s[(4 - i) & 7] = job.ce + v; s[(5 - i) & 7] = job.st[4]; s[(6 - i) & 7] = job.st[5];
+        s[(3 - i) & 7] = x1 + lc.ch + sc.se;           // e12 = d + t1
+        s[(7 - i) & 7] = (x1 + x0 + lc.cm) + sc.sa;  // a12 = t1 + t2
+    }
+    pow_sched_open_rounds<2, O::R0 + 2, O::FIRST>(job, r);
+    pow_sched_pinned<O, FILL>(job, r, sc);
+    return r.s[(0 - 64) & 7];
+}
+
+// One nonce word through the split function (the tests' H0 of variant 10): the word as lane << 26 | U
+__host__ __device__ __forceinline__ uint32_t pow_h0_split(const PowJobDev& job, uint32_t v) {
+    const uint32_t p = 26, lane = v >> p, sv = v & ((1u << p) - 1u);
+    PowSplitCache cached;
+    PowSplitLane lc;
+    pow_split_prologue(job, p, sv, lane, cached, lc);
+    return job.mid[0] + pow_a_split<2>(job, p, sv, lane, cached, lc);
+}
+
 
 // Variant 2 (A/B evidence for the design note above): the same v2 search with the expanded message
 // schedule W16..W63 staged in LDS instead of VGPRs. Each lane owns a 16-word ring in LDS laid out
@@ -569,12 +870,51 @@ __global__ __launch_bounds__(256, MIN_WAVES_PER_SIMD) void pow_search_sched_kern
     }
 }
 
+// Variant 10. One dispatch covers U in [u_begin, u_end) of the piece v = vb + U + (lane << p): wave w of the grid
+// (four per block) takes the `iters` values from u_begin + w * iters on, cut at u_end. The host keeps
+// (waves + 3) * iters below 2^32. RANGE: the job's hit predicate is the one range check (PowJobDev::range_ok).
+template <bool RANGE>
+__global__ __launch_bounds__(256, 8) void pow_search_split_kernel(PowJobDev job, uint32_t vb, uint32_t p, uint32_t u_begin,
+                                                                  uint32_t u_end, uint32_t iters,
+                                                                  uint32_t* __restrict__ out_count,
+                                                                  uint32_t* __restrict__ out_words, uint32_t cap) {
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t u = u_begin + wave * iters;
+    if (u >= u_end) return;
+    const uint32_t u_stop = u_end - u < iters ? u_end : u + iters;
+    PowSplitCache cached;
+    PowSplitLane lc;
+    pow_split_prologue(job, p, vb + u, lane, cached, lc);
+    for (; u < u_stop; ++u) {
+        const uint32_t sv = vb + u;
+        const uint32_t a = pow_a_split<2>(job, p, sv, lane, cached, lc);
+        bool hit;
+        if (RANGE) {
+            hit = a + job.range_base < job.range_width;
+        } else {
+            const uint32_t h0 = job.mid[0] + a;
+            hit = ((h0 ^ job.tword) & job.tmask) == 0 && ((h0 >> job.frac_shift) & 0xfu) < job.frac_limit;
+        }
+        if (__builtin_expect(hit, 0)) {
+            const uint32_t slot = atomicAdd(out_count, 1u);
+            if (slot < cap) out_words[slot] = sv + lc.lanep;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 static void hip_check(hipError_t e, const char* what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
+
+// Variant 10 cuts a range into pieces of 2^(p+6) nonce words, kPowSplitMinLog2 <= p <= kPowSplitMaxLog2. 26 is a
+// whole sweep (six bits of the word are the lane index). Below 2^14 words a piece is at most 256 wave-iterations
+// behind a prologue of its own and a dispatch of its own, and the unsplit kernel does all of what is left in one
+// launch, so the rest of a range (fewer than 2^14 words) goes to it.
+constexpr int kPowSplitMinLog2 = 8, kPowSplitMaxLog2 = 26;
 
 PowJobDev make_pow_job(const PowJobHost& hj) {
     PowJobDev j{};
@@ -636,7 +976,67 @@ PowJobDev make_pow_job(const PowJobHost& hj) {
             j.hk[k] = s[6 - k] + (kinds.vec[i] ? kSha256K[i] : j.kw[i]);
         }
     }
+    // variant 10 (108-byte header)
+    j.c24 = j.kw[24] + j.kw[17];
+    j.he = j.st[2] + j.hk[0];
+    j.fxg = j.st[4] ^ j.st[5];
+    j.bxc = j.st[0] ^ j.st[1];
+    // The predicate ((H0 ^ tword) & tmask) == 0 && ((H0 >> frac_shift) & 15) < frac_limit is tword <= H0 <
+    // tword + width where tmask is the nibbles above the fractional one (width = frac_limit << frac_shift) or,
+    // with no fractional nibble, a prefix from the top of the word (width = its lowest set bit).
+    {
+        uint32_t width = 0;
+        bool ok = false;
+        if (j.frac_limit < 16) {
+            const uint32_t above = j.frac_shift + 4 >= 32 ? 0u : ~((1u << (j.frac_shift + 4)) - 1u);
+            ok = j.frac_shift <= 28 && j.tmask == above;
+            width = j.frac_limit << (j.frac_shift & 31);
+        } else if (j.tmask != 0) {
+            width = j.tmask & (0u - j.tmask);
+            ok = j.tmask == 0u - width;
+        }
+        ok = ok && width != 0 && (j.tword & ~j.tmask) == 0;
+        j.range_ok = ok ? 1 : 0;
+        j.range_base = j.mid[0] - j.tword;
+        j.range_width = ok ? width : 0;
+    }
     return j;
+}
+
+PowSplitConsts pow_split_consts(const PowJobHost& hj) {
+    if (hj.header.size() != 108) throw std::invalid_argument("the split kernel is for the 108-byte header");
+    const PowJobDev j = make_pow_job(hj);
+    PowSplitConsts c;
+    c.ca = j.ca; c.ce = j.ce; c.c17 = j.kw[17]; c.c24 = j.c24;
+    c.mid0 = j.mid[0];
+    c.range_ok = j.range_ok != 0;
+    c.range_base = j.range_base;
+    c.range_width = j.range_width;
+    c.min_log2 = kPowSplitMinLog2;
+    c.max_log2 = kPowSplitMaxLog2;
+    return c;
+}
+
+bool pow_range_hit_host(const PowJobHost& hj, uint32_t h0) {
+    const PowJobDev j = make_pow_job(hj);
+    if (!j.range_ok) throw std::invalid_argument("this job's predicate has no range form");
+    const uint32_t a = h0 - j.mid[0];  // the kernel has a, not H0
+    return a + j.range_base < j.range_width;
+}
+
+std::vector<uint32_t> pow_split_wave_host(const PowJobHost& hj, uint32_t vb, uint32_t p, uint32_t u_first,
+                                          uint32_t iters) {
+    if (hj.header.size() != 108) throw std::invalid_argument("the split kernel is for the 108-byte header");
+    if (p > uint32_t(kPowSplitMaxLog2)) throw std::invalid_argument("p must be at most 26: the lane index takes six bits");
+    const PowJobDev job = make_pow_job(hj);
+    PowSplitCache cached[64];
+    PowSplitLane lc[64];
+    for (uint32_t lane = 0; lane < 64; ++lane) pow_split_prologue(job, p, vb + u_first, lane, cached[lane], lc[lane]);
+    std::vector<uint32_t> out(size_t(iters) * 64);
+    for (uint32_t it = 0; it < iters; ++it)
+        for (uint32_t lane = 0; lane < 64; ++lane)
+            out[size_t(it) * 64 + lane] = job.mid[0] + pow_a_split<2>(job, p, vb + u_first + it, lane, cached[lane], lc[lane]);
+    return out;
 }
 
 // H0 of SHA256(header with nonce word v) through pow_h0_pre on the host: the kernel's arithmetic on the
@@ -678,16 +1078,27 @@ static PowDeviceBuffers& pow_buffers(uint32_t cap) {
 //  6-9  variant 5's instructions in a pinned order (pow_h0_sched), W[i+2] produced during round i, 8 waves/SIMD:
 //     6  two-path rounds: next to no instruction follows its producer      7  rounds path after path
 //     8  as 7 with an s_sleep 0 in front of every rotate      9  as 7 with one in front of every rotate and add3
+//  10  variant 9 with the lane index in the top bits of the nonce word (pow_a_split, pow_search_split_kernel): the
+//     wave-uniform low bits of W10, W17, W24, a11 and e11 go through the SALU, one scalar instruction in the place
+//     of one filler; their per-lane high bits are loop-invariant VGPRs, and the hit predicate is one range check.
+//     Pieces of 2^14..2^32 words; what is left of a range below 2^14 words runs on variant 9's kernel
 //  0  the default, kPowDefaultVariant
 // v1 headers have the original loop (1-3) and the precomputed one (4 and up) only.
-constexpr int kPowDefaultVariant = 9;
-constexpr int kPowVariantCount = 10;
+constexpr int kPowDefaultVariant = 10;
+constexpr int kPowSplitVariant = 10;
+constexpr int kPowVariantCount = 11;
 
 using PowKernelFn = void (*)(PowJobDev, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t);
 
-static PowKernelFn pow_kernel_fn(bool v2, int variant) {
+static int pow_resolve_variant(int variant) {
     if (variant < 0 || variant >= kPowVariantCount) throw std::invalid_argument("unknown PoW kernel variant");
-    if (variant == 0) variant = kPowDefaultVariant;
+    return variant == 0 ? kPowDefaultVariant : variant;
+}
+
+// The grid-strided kernel of a variant; for variant 10 the one that runs what its pieces leave over
+static PowKernelFn pow_kernel_fn(bool v2, int variant) {
+    variant = pow_resolve_variant(variant);
+    if (v2 && variant == kPowSplitVariant) variant = 9;
     // v1 at 7 waves/SIMD: left to itself the compiler takes 106 SGPRs and spills some to VGPR lanes in the loop
     if (!v2) return variant >= 4 ? &pow_search_pre_kernel<1, 7> : &pow_search_kernel<1, 1>;
     switch (variant) {
@@ -716,6 +1127,7 @@ uint32_t pow_job_h0_host(const PowJobHost& hj, uint32_t v, int variant) {
         case 7: return pow_h0_sched<2, 2, false, 0>(job, v);
         case 8: return pow_h0_sched<2, 2, false, 1>(job, v);
         case 9: return pow_h0_sched<2, 2, false, 2>(job, v);
+        case 10: return pow_h0_split(job, v);
         default: return pow_h0_pre<2>(job, v);
     }
 }
@@ -726,7 +1138,9 @@ static int pow_resident_blocks(bool v2, int variant) {
     int dev = 0, cus = 0, per_cu = 0;
     hip_check(hipGetDevice(&dev), "hipGetDevice");
     hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "attr");
-    const void* fn = reinterpret_cast<const void*>(pow_kernel_fn(v2, variant));
+    const void* fn = v2 && pow_resolve_variant(variant) == kPowSplitVariant
+                         ? reinterpret_cast<const void*>(&pow_search_split_kernel<true>)
+                         : reinterpret_cast<const void*>(pow_kernel_fn(v2, variant));
     hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0), "occupancy");
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
@@ -766,6 +1180,30 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
         chunk_iters = uint32_t(std::max<uint64_t>(1, (uint64_t(1) << lg) / per_launch_threads));
     }
     uint64_t done = 0;
+    if (v2 && pow_resolve_variant(variant) == kPowSplitVariant) {
+        // Maximal power-of-two pieces, largest first; grid_blocks and chunk_iters keep their meaning: blocks per
+        // dispatch and iterations (values of U) per wave per dispatch. A piece smaller than a dispatch is spread
+        // over as many waves as it has iterations for.
+        const auto split = job.range_ok ? &pow_search_split_kernel<true> : &pow_search_split_kernel<false>;
+        const uint64_t waves = uint64_t(grid_blocks) * (block / 64);
+        while (count - done >= (uint64_t(1) << (kPowSplitMinLog2 + 6))) {
+            int lg = 63 - __builtin_clzll(count - done);
+            const uint32_t p = uint32_t(std::min(lg - 6, kPowSplitMaxLog2));
+            const uint32_t vb = uint32_t(start + done), n_u = uint32_t(1) << p;
+            for (uint32_t u = 0; u < n_u;) {
+                const uint32_t left = n_u - u;
+                const uint32_t iters = uint32_t(std::min<uint64_t>(chunk_iters, (left + waves - 1) / waves));
+                const uint64_t need = (uint64_t(left) + iters - 1) / iters;  // waves that have an iteration
+                const uint32_t gb = uint32_t(std::min<uint64_t>(uint64_t(grid_blocks), (need + 3) / 4));
+                const uint32_t u_end = uint32_t(std::min<uint64_t>(n_u, u + uint64_t(gb) * 4 * iters));
+                hipLaunchKernelGGL(split, dim3(gb), dim3(block), 0, st, job, vb, p, u, u_end, iters, buf.d_count,
+                                   buf.d_words, cap);
+                hip_check(hipGetLastError(), "pow_search_split_kernel launch");
+                u = u_end;
+            }
+            done += uint64_t(1) << (p + 6);
+        }
+    }
     while (done < count) {
         const uint64_t left = count - done;
         uint32_t iters = chunk_iters;

@@ -27,7 +27,7 @@ CLASSES = [('rotate (v_alignbit_b32)', r'^v_alignbit_b32'), ('bitop3 (XOR3 / Maj
            ('add3 (v_add3_u32)', r'^v_add3_u32'), ('add (v_add_u32)', r'^v_add_u32|^v_add_co_u32|^v_add_nc_u32'),
            ('shift (v_lshrrev_b32)', r'^v_lshrrev_b32|^v_lshlrev_b32'), ('bfi / cndmask', r'^v_bfi_b32|^v_cndmask'),
            ('compare', r'^v_cmp'), ('other VALU', r'^v_'), ('LDS', r'^ds_'), ('memory', r'^(global|buffer|flat)_'),
-           ('SALU / branch', r'^s_')]
+           ('filler (s_sleep / s_nop)', r'^s_sleep|^s_nop'), ('SALU / branch', r'^s_')]
 
 
 def compile_asm() -> str:
@@ -36,6 +36,51 @@ def compile_asm() -> str:
                     '--cuda-device-only', '-S', os.path.join(ROOT, 'csrc', 'pow_search.hip'), '-o', out], check=True,
                    stderr=subprocess.DEVNULL)
     return open(out).read()
+
+
+HIT_TEST = r's_cbranch_exec(n)?z'
+
+
+def cheapest_path(loop: str) -> list:
+    """The instructions of one iteration that takes no optional work: the loop cut into basic blocks, and from
+    the header to the block that ends in the hit test the path with the fewest VALU instructions. A loop of one
+    block is that block. The split kernel (variant 10) recomputes lane constants in blocks of their own when a
+    carry flips; the path found here is the iteration in which none does."""
+    blocks, names = [[]], {}
+    for ln in loop.splitlines():
+        m = re.match(r'^(\.LBB\w+):', ln)
+        if m:
+            if blocks[-1]:
+                blocks.append([])
+            names[m.group(1)] = len(blocks) - 1
+            continue
+        if not re.match(r'^\s+[a-z]', ln) or ln.strip().startswith(';'):
+            continue
+        blocks[-1].append(ln.split())
+        if re.match(r's_cbranch|s_branch', ln.split()[0]):
+            blocks.append([])
+    last = next((i for i, b in enumerate(blocks) if b and re.match(HIT_TEST, b[-1][0])), len(blocks) - 1)
+    cost = lambda b: (sum(1 for t in b if t[0].startswith('v_')), len(b))
+    best = {0: (cost(blocks[0]), [0])}
+    todo = [0]
+    while todo:
+        i = todo.pop()
+        if i == last or not blocks[i]:
+            succ = [] if i == last else [i + 1]
+        else:
+            op = blocks[i][-1]
+            tgt = names.get(op[1]) if len(op) > 1 else None
+            succ = [tgt] if op[0] == 's_branch' else [tgt, i + 1] if op[0].startswith('s_cbranch') else [i + 1]
+        for j in succ:
+            if j is None or j > last or j <= 0:
+                continue
+            c = tuple(a + b for a, b in zip(best[i][0], cost(blocks[j])))
+            if j not in best or c < best[j][0]:
+                best[j] = (c, best[i][1] + [j])
+                todo.append(j)
+    path = best.get(last, (None, list(range(last + 1))))[1]
+    ins = [t[0] for i in path for t in blocks[i]]
+    return ins[:-1] if ins and re.match(HIT_TEST, ins[-1]) else ins
 
 
 def loop_bodies(asm: str) -> dict:
@@ -53,9 +98,9 @@ def loop_bodies(asm: str) -> dict:
         if not hdr:
             continue
         loop = body[hdr.end():]
-        stop = re.search(r's_cbranch_execz', loop)  # the hit test: everything before it runs once per nonce
-        loop = loop[:stop.start()] if stop else loop
-        ins = [ln.split()[0] for ln in loop.splitlines() if re.match(r'^\s+[a-z]', ln) and not ln.strip().startswith(';')]
+        stop = re.search(HIT_TEST, loop)  # the hit test: everything before it runs once per nonce
+        loop = loop[:stop.end()] if stop else loop
+        ins = cheapest_path(loop)
         out[name] = (ins, int(vg.group(1)) if vg else None, int(occ.group(1)) if occ else None)
         del tail
     return out
@@ -83,13 +128,14 @@ def floor_v2() -> dict:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--asm', default=None, help='read this assembly file instead of compiling the kernel TU')
     a = ap.parse_args()
-    asm = compile_asm()
+    asm = open(a.asm).read() if a.asm else compile_asm()
     lines = ['# PoW search loop: instructions per nonce (one loop iteration = one nonce per lane)',
              f'# source csrc/pow_search.hip, hipcc --offload-arch=gfx950 -O3 (scripts/pow_isa_audit.py)', '']
     for name, (ins, vgpr, occ) in loop_bodies(asm).items():
         c = classify(ins)
-        valu = sum(v for k, v in c.items() if k not in ('LDS', 'memory', 'SALU / branch'))
+        valu = sum(v for k, v in c.items() if k not in ('LDS', 'memory', 'filler (s_sleep / s_nop)', 'SALU / branch'))
         lines.append(f'{name}  (VGPRs {vgpr}, occupancy {occ} waves/SIMD)')
         for k, v in c.items():
             if v:
