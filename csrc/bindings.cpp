@@ -170,13 +170,18 @@ PYBIND11_MODULE(_native, m) {
           py::arg("header"), py::arg("tmask"), py::arg("tword"), py::arg("frac_shift"), py::arg("frac_limit"),
           py::arg("h0"), "variant 10's one-compare hit predicate on a digest word H0 (range_ok jobs only)");
 
-    m.def("pow_split_wave", [](py::bytes header, uint32_t vb, uint32_t p, uint32_t u_first, uint32_t iters) {
-        const std::vector<uint32_t> h = pow_split_wave_host(make_job(header, 0, 0, 0, 16), vb, p, u_first, iters);
+    m.def("pow_range_hit_folded", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
+                                     uint32_t h0) { return pow_range_hit_folded_host(make_job(header, tmask, tword, fs, fl), h0); },
+          py::arg("header"), py::arg("tmask"), py::arg("tword"), py::arg("frac_shift"), py::arg("frac_limit"),
+          py::arg("h0"), "variant 11's hit compare, range_base folded into round 63's constant (range_ok jobs only)");
+
+    m.def("pow_split_wave", [](py::bytes header, uint32_t vb, uint32_t p, uint32_t u_first, uint32_t iters, int variant) {
+        const std::vector<uint32_t> h = pow_split_wave_host(make_job(header, 0, 0, 0, 16), vb, p, u_first, iters, variant);
         py::array_t<uint32_t> out({py::ssize_t(iters), py::ssize_t(64)});
         std::memcpy(out.mutable_data(), h.data(), h.size() * sizeof(uint32_t));
         return out;
-    }, py::arg("header"), py::arg("vb"), py::arg("p"), py::arg("u_first"), py::arg("iters"),
-       "variant 10's wave loop on the host: H0[iteration][lane] for nonce words vb + U + (lane << p), "
+    }, py::arg("header"), py::arg("vb"), py::arg("p"), py::arg("u_first"), py::arg("iters"), py::arg("variant") = 0,
+       "variant 10's or 11's (0: the default's) wave loop on the host: H0[iteration][lane] for nonce words vb + U + (lane << p), "
        "U = u_first .. u_first + iters - 1, with the kernel's cached lane constants");
 
     m.def("pow_search_host", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,

@@ -41,10 +41,13 @@ struct PowSplitConsts {
 PowSplitConsts pow_split_consts(const PowJobHost& job);
 // The kernel's range form of the hit predicate on a given H0 (range_ok jobs only)
 bool pow_range_hit_host(const PowJobHost& job, uint32_t h0);
-// The wave loop of variant 10 on the host: 64 lanes with cached lane constants that are recomputed when a carry
-// flips, U = u_first .. u_first + iters - 1. Returns H0 of every lane per iteration, [iteration][lane].
+// The same for variant 11's kernel, whose round 63 adds range_base with K[63]: the compare it is left with
+bool pow_range_hit_folded_host(const PowJobHost& job, uint32_t h0);
+// The wave loop of variant 10 or 11 (0: the default variant) on the host: 64 lanes with cached lane constants that
+// are recomputed when a carry flips, U = u_first .. u_first + iters - 1. Returns H0 of every lane per iteration,
+// [iteration][lane].
 std::vector<uint32_t> pow_split_wave_host(const PowJobHost& job, uint32_t vb, uint32_t p, uint32_t u_first,
-                                          uint32_t iters);
+                                          uint32_t iters, int variant = 0);
 
 bool pow_check_word_host(const PowJobHost& job, uint32_t v);
 PowResult pow_search_host(const PowJobHost& job, uint64_t start, uint64_t count, int threads);

@@ -25,11 +25,15 @@
 //  * variant 9 (pow_h0_sched) issues pow_h0_pre's instructions in a pinned order with an s_sleep 0 in front of
 //    every v_alignbit_b32 and v_add3_u32: behind that sequencer-only instruction the two slow opcodes cost about
 //    a cycle less (3.66 against 3.94 cycles per VALU instruction, docs/PERF.md);
-//  * the default v2 kernel (pow_a_split, variant 10) is variant 9 with the lane index in the TOP bits of the nonce
+//  * variant 10 (pow_a_split) is variant 9 with the lane index in the TOP bits of the nonce
 //    word, v = vb + U + (lane << p): what all 64 lanes of a wave would compute alike (the low p bits of W10, a11,
 //    e11, W17, W24 and their sigmas, round 11's Ch and Maj) is done once per wave on the SALU, one scalar
 //    instruction in the place of one s_sleep 0, and the per-lane high bits are loop-invariant VGPRs: 1,085 VALU
 //    instructions per nonce against 1,108, 446 rotates against 462 (docs/PERF.md, "PoW lane/uniform split");
+//  * the default v2 kernel (pow_a_fill, variant 11) is variant 10 with exactly one scalar or sequencer instruction in
+//    front of every v_alignbit_b32 and v_add3_u32 and none doubled up: each K[i] is loaded in a scalar slot of its own,
+//    rounds 12 and 13 are pinned too, and the nonce word, W17 and the range check's add are not VALU instructions any
+//    more: 1,082 VALU instructions per nonce (docs/PERF.md, "PoW scalar slots");
 //  * the predicate only needs digest word H0 for difficulty < 8 (8 hex nibbles) -> one compare per
 //    nonce (variant 10: one add and one unsigned compare, (H0 - tword) < width); hits are appended with an atomic to a small candidate list and re-checked exactly on the
 //    host (covers d >= 8 and the d < 1 "whole hash" quirk).
@@ -68,6 +72,16 @@ struct PowJobDev {
     // a + range_base < range_width. range_ok = 0: the mask is no prefix or the width no 32-bit number.
     uint32_t range_ok, range_base, range_width;
 };
+// What variant 11 adds to the job constants. An argument of its own kernels: PowJobDev keeps its size, and with it
+// the other variants' kernels their code.
+struct PowFillDev {
+    uint32_t k17w;     // round 17: h + K[17] + W17 = h + (k17w + sv) + lanep, k17w = K[17] + kw[17]
+    uint32_t c33;      // W33's first add: kw[33] + W17 = (c33 + sv) + lanep, c33 = kw[33] + kw[17]
+    uint32_t k63r;     // round 63's K with the range check's base in it: the loop ends in a + range_base
+};
+__host__ __device__ __forceinline__ PowFillDev make_pow_fill(const PowJobDev& j) {
+    return {kSha256K[17] + j.kw[17], j.kw[33] + j.kw[17], kSha256K[63] + j.range_base};
+}
 
 // Which words of the tail block's message schedule depend on the nonce (vec) and, of those, which also have
 // nonce-independent terms (has_const). Shared by the host precomputation and the unrolled device loop.
@@ -229,6 +243,10 @@ struct PowSchedRegs {
     // per-lane high bits (xl, VGPRs that do not change from iteration to iteration); sigma = xs ^ xl.
     //  0 sigma0(W10)   1 sigma1(W17)   2 sigma0(W17)   3 sigma1(W24)   4 sigma0(W24)
     uint32_t xs[5], xl[5];
+    // G11 (variant 11) only: the K word (or scalar sum) that the coming h + K + W reads, loaded in the scalar slot
+    // in front of it; lane << p; and the wave-uniform parts c24 + sv, kw[26] + sv, c33 + sv of the sums that take
+    // the nonce word as (uniform part) + lanep
+    uint32_t kx, lanep, us[3];
 };
 // Index into xs / xl of sigma0(W[j-15]) and of sigma1(W[j-2]), or -1 where the word is not split
 constexpr int pow_split_s0(int j) { return j - 15 == 10 ? 0 : j - 15 == 17 ? 2 : j - 15 == 24 ? 4 : -1; }
@@ -245,8 +263,10 @@ struct PowOpRegs {
 // Instruction k (0..9) of schedule word W[j]; instructions of terms that are nonce independent do not exist.
 //  0-3 sigma0(W[j-15]) -> t[0]    4-7 sigma1(W[j-2]) -> t[1]    8 the first add of a four-term sum    9 W[j]
 // split: a split word's sigma is one XOR, xs ^ xl, in the place of the XOR3 (k = 3 / 7); its rotates and shift go
-constexpr bool pow_sched_op_exists(const PowWordKinds& kinds, int j, int k, bool split = false) {
+// g11: W17 = kw[17] + v is not made; each of its readers takes (its own constant + sv) + lanep instead.
+constexpr bool pow_sched_op_exists(const PowWordKinds& kinds, int j, int k, bool split = false, bool g11 = false) {
     if (j < 16 || j > 63 || !kinds.vec[j]) return false;
+    if (g11 && j == 17) return false;
     if (k < 4) return kinds.vec[j - 15] && !(split && pow_split_s0(j) >= 0 && k < 3);
     if (k < 8) return kinds.vec[j - 2] && !(split && pow_split_s1(j) >= 0 && k < 7);
     const int n = int(kinds.has_const[j]) + int(kinds.vec[j - 16]) + int(kinds.vec[j - 15]) + int(kinds.vec[j - 7]) +
@@ -255,11 +275,16 @@ constexpr bool pow_sched_op_exists(const PowWordKinds& kinds, int j, int k, bool
 }
 
 // RUN: execute the instruction; otherwise only name its registers
-template <int LAYOUT, int J, int K, bool RUN, bool SPLIT = false>
+template <int LAYOUT, int J, int K, bool RUN, bool SPLIT = false, bool G11 = false>
 __host__ __device__ __forceinline__ PowOpRegs pow_sched_op(const PowJobDev& job, PowSchedRegs& r) {
     constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
     PowOpRegs o;
-    if constexpr (pow_sched_op_exists(kinds, J, K, SPLIT)) {
+    if constexpr (G11 && ((J == 24 && K == 9) || (J == 26 && K == 8) || (J == 33 && K == 8))) {
+        // W24 = c24 + v, and the first adds of W26 (kw[26] + W10) and W33 (kw[33] + W17): an SGPR plus lanep
+        constexpr int n = J == 24 ? 0 : J == 26 ? 1 : 2;
+        o = {{nullptr, nullptr, nullptr}, J == 24 ? &r.w[J & 15] : &r.t[2]};
+        if (RUN) *o.out = r.us[n] + r.lanep;
+    } else if constexpr (pow_sched_op_exists(kinds, J, K, SPLIT, G11)) {
         constexpr int j = J, k = K;
         constexpr bool c = kinds.has_const[j], v16 = kinds.vec[j - 16], v15 = kinds.vec[j - 15],
                        v7 = kinds.vec[j - 7], v2 = kinds.vec[j - 2];
@@ -314,17 +339,26 @@ __host__ __device__ __forceinline__ PowOpRegs pow_sched_op(const PowJobDev& job,
 // the next e takes d's.
 enum PowRoundOp { R_X, R_R1, R_R2, R_R3, R_CH, R_S1, R_T1, R_E, R_Q1, R_Q2, R_Q3, R_S0, R_MJ, R_A };
 
-template <int LAYOUT, int I, int OP, bool RUN>
+// G11: K comes from r.kx; round 17 reads lanep for W17 (r.kx holds the rest); rounds 12 and 13 are pinned too, where
+// h is still a job constant (folded into hk, no R_X) and c, d, g (round 12) and d (round 13) are as well: SGPR
+// operands, which no fence names.
+template <int LAYOUT, int I, int OP, bool RUN, bool G11 = false>
 __host__ __device__ __forceinline__ PowOpRegs pow_round_op(const PowJobDev& job, PowSchedRegs& r) {
     constexpr PowWordKinds kinds = pow_word_kinds(LAYOUT);
     constexpr int i = I;
+    constexpr bool early = G11 && i < 14;  // h uniform
     uint32_t(&s)[8] = r.s;
     uint32_t(&u)[4] = r.u;
     uint32_t(&q)[3] = r.q;
     uint32_t &a = s[(0 - i) & 7], &b = s[(1 - i) & 7], &c = s[(2 - i) & 7], &d = s[(3 - i) & 7];
     uint32_t &e = s[(4 - i) & 7], &f = s[(5 - i) & 7], &g = s[(6 - i) & 7], &h = s[(7 - i) & 7];
     PowOpRegs o;
-    if constexpr (OP == R_X) {
+    if constexpr (OP == R_X && G11) {
+        if constexpr (!early) {
+            o = {{&h, kinds.vec[i] && i != 17 ? &r.w[i & 15] : nullptr, nullptr}, &h};
+            if (RUN) h = i == 17 ? h + r.kx + r.lanep : kinds.vec[i] ? h + r.kx + r.w[i & 15] : h + job.kw[i];
+        }
+    } else if constexpr (OP == R_X) {
         o = {{&h, kinds.vec[i] ? &r.w[i & 15] : nullptr, nullptr}, &h};
         if (RUN) h = kinds.vec[i] ? h + kSha256K[i] + r.w[i & 15] : h + job.kw[i];
     } else if constexpr (OP == R_R1) {
@@ -337,17 +371,17 @@ __host__ __device__ __forceinline__ PowOpRegs pow_round_op(const PowJobDev& job,
         o = {{&e, nullptr, nullptr}, &u[2]};
         if (RUN) u[2] = P_ROTR(e, 25);
     } else if constexpr (OP == R_CH) {
-        o = {{&e, &f, &g}, &u[3]};
+        o = {{&e, &f, G11 && i == 12 ? nullptr : &g}, &u[3]};
         if (RUN) u[3] = P_CH(e, f, g);
     } else if constexpr (OP == R_S1) {
         o = {{&u[2], &u[1], &u[0]}, &u[0]};
         if (RUN) u[0] = P_XOR3(u[0], u[1], u[2]);
     } else if constexpr (OP == R_T1) {
-        o = {{&u[0], &u[3], &h}, &h};
-        if (RUN) h = h + u[0] + u[3];
+        o = {{&u[0], &u[3], early ? nullptr : &h}, &h};
+        if (RUN) h = (early ? job.hk[(i - 11) % 3] : h) + u[0] + u[3];
     } else if constexpr (OP == R_E) {
         if constexpr (i != 63) {  // nothing reads the last e
-            o = {{&h, &d, nullptr}, &d};
+            o = {{&h, early ? nullptr : &d, nullptr}, &d};
             if (RUN) d = d + h;
         }
     } else if constexpr (OP == R_Q1) {
@@ -363,7 +397,7 @@ __host__ __device__ __forceinline__ PowOpRegs pow_round_op(const PowJobDev& job,
         o = {{&q[2], &q[1], &q[0]}, &q[0]};
         if (RUN) q[0] = P_XOR3(q[0], q[1], q[2]);
     } else if constexpr (OP == R_MJ) {
-        o = {{&a, &b, &c}, &q[1]};
+        o = {{&a, &b, G11 && i == 12 ? nullptr : &c}, &q[1]};
         if (RUN) q[1] = P_MAJ(a, b, c);
     } else {
         o = {{&q[1], &q[0], &h}, &h};
@@ -382,9 +416,14 @@ __host__ __device__ __forceinline__ void pow_static_for(F&& f) {
     pow_static_for<B>(f, std::make_integer_sequence<int, (E > B ? E - B : 0)>{});
 }
 
-template <int LAYOUT, int D, bool TWO_PATH, bool SPLIT = false>
+// G11 (variant 11): rounds 12 and 13 are pinned as well, K[i] is loaded by a scalar slot of its own (k_slot), and
+// the first step of all has a filler in front of it too.
+template <int LAYOUT, int D, bool TWO_PATH, bool SPLIT = false, bool G11 = false>
 struct PowOrder {
-    static constexpr int R0 = 10, FIRST = R0 + 4;  // first round whose whole state is nonce dependent
+    // first pinned round. R0 + 4 is the first round whose whole state is nonce dependent
+    static constexpr int R0 = 10, FIRST = G11 ? R0 + 2 : R0 + 4;
+    static constexpr bool kG11 = G11;
+    static constexpr PowWordKinds kKinds = pow_word_kinds(LAYOUT);
     static constexpr int SLOTS = 24, STEPS = (64 - FIRST) * SLOTS;
     static constexpr int kOnePath[14] = {R_X, R_R1, R_R2, R_R3, R_CH, R_S1, R_T1, R_Q1, R_E, R_Q2, R_Q3, R_S0, R_MJ, R_A};
     static constexpr int kTwoPath[14] = {R_R1, R_Q1, R_R2, R_Q2, R_R3, R_Q3, R_CH, R_S1, R_X, R_S0, R_T1, R_MJ, R_E, R_A};
@@ -401,13 +440,21 @@ struct PowOrder {
     }
     static constexpr bool exists(int g) {
         if (g < 0 || g >= STEPS) return false;
-        if (is_sched(g)) return pow_sched_op_exists(pow_word_kinds(LAYOUT), round_of(g) + D, sched_k(g), SPLIT);
+        if (is_sched(g)) return pow_sched_op_exists(kKinds, round_of(g) + D, sched_k(g), SPLIT, G11);
+        if (G11 && round_op(g) == R_X && round_of(g) < R0 + 4) return false;  // h is a constant, folded into hk
         return !(round_op(g) == R_E && round_of(g) == 63);
     }
+    // An h + K[i] + W[i] that reads its K from PowSchedRegs::kx, and the step whose scalar slot loads that K: the
+    // one before it (the round before's last add3), not its own, because an SGPR that an asm statement defines
+    // costs an s_nop when the very next instruction reads it.
+    static constexpr bool reads_kx(int g) {
+        return G11 && exists(g) && !is_sched(g) && round_op(g) == R_X && kKinds.vec[round_of(g)];
+    }
+    static constexpr bool k_slot(int g) { return G11 && g >= 0 && exists(g) && slow(g) && reads_kx(next(g)); }
     // v_alignbit_b32 and v_add3_u32 issue at 4.1 cycles, everything else here at 2.3 (docs/PERF.md)
     static constexpr bool slow(int g) {
         if (!exists(g)) return false;
-        const PowWordKinds kinds = pow_word_kinds(LAYOUT);
+        const PowWordKinds& kinds = kKinds;
         if (is_sched(g)) {
             const int k = sched_k(g), j = round_of(g) + D;
             if (k < 8) return (k & 3) < 2;
@@ -449,18 +496,53 @@ struct PowOrder {
     template <int G, bool RUN>
     static __host__ __device__ __forceinline__ PowOpRegs op(const PowJobDev& job, PowSchedRegs& r) {
         if constexpr (!exists(G)) return {};
-        else if constexpr (is_sched(G)) return pow_sched_op<LAYOUT, round_of(G) + D, sched_k(G), RUN, SPLIT>(job, r);
-        else return pow_round_op<LAYOUT, round_of(G), round_op(G), RUN>(job, r);
+        else if constexpr (is_sched(G)) return pow_sched_op<LAYOUT, round_of(G) + D, sched_k(G), RUN, SPLIT, G11>(job, r);
+        else return pow_round_op<LAYOUT, round_of(G), round_op(G), RUN, G11>(job, r);
     }
 };
+
+// G11: the fillers that take a step of the scalar program are numbered without gaps, a round's first
+// kUopsPerRound fillers that are no K slot and not in front of the first step (a round whose last add3 loads the
+// next round's K can have fewer than that many left). at[g]: the number of the filler in front of step g, or -1;
+// first[i]: the number of round i's first such filler.
+template <class O>
+struct PowUopTable {
+    struct T { int at[O::STEPS]; int first[64]; };
+    static constexpr T make() {
+        T t{};
+        const int first = O::exists(0) ? 0 : O::next(0);
+        int n = 0, local = 0;
+        for (int i = 0; i < 64; ++i) t.first[i] = -1;
+        for (int g = 0; g < O::STEPS; ++g) {
+            if (g % O::SLOTS == 0) local = 0;
+            t.at[g] = -1;
+            if (g == first || !O::fill_before(2, g) || O::k_slot(g)) continue;
+            if (local++ < O::kUopsPerRound) {
+                if (t.first[O::round_of(g)] < 0) t.first[O::round_of(g)] = n;
+                t.at[g] = n++;
+            }
+        }
+        return t;
+    }
+    static constexpr T k = make();
+};
+template <class O>
+constexpr int pow_uop_index(int fill, int g) {
+    if constexpr (O::kG11) return g >= 0 && fill == 2 ? PowUopTable<O>::k.at[g] : -1;
+    else return O::uop_index(fill, g);
+}
+using PowFillOrder = PowOrder<2, 2, false, true, true>;
 
 template <int LAYOUT, int FROM, int TO>
 __host__ __device__ __forceinline__ void pow_sched_open_rounds(const PowJobDev& job, PowSchedRegs& r);
 // The scalar program of a pinned loop: uop<N> is one SALU instruction that goes into filler N's place
 struct PowNoScalar {
     static constexpr int kCount = 0;
+    static constexpr bool has(int) { return false; }
     template <int N>
     __host__ __device__ __forceinline__ void uop(const PowJobDev&, PowSchedRegs&) {}
+    template <int I>
+    __host__ __device__ __forceinline__ uint32_t kx(const PowJobDev&) const { return kSha256K[I]; }
 };
 template <class O, int FILL, class S>
 __host__ __device__ __forceinline__ void pow_sched_pinned(const PowJobDev& job, PowSchedRegs& r, S& sc);
@@ -530,12 +612,20 @@ __host__ __device__ __forceinline__ void pow_sched_open_rounds(const PowJobDev& 
 // slow one does what the filler does (docs/PERF.md, "PoW lane/uniform split").
 template <class O, int FILL, class S>
 __host__ __device__ __forceinline__ void pow_sched_pinned(const PowJobDev& job, PowSchedRegs& r, S& sc) {
+    if constexpr (O::FIRST < O::R0 + 4) {  // G11: the first step's filler
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (O::fill_before(FILL, O::exists(0) ? 0 : O::next(0))) __builtin_amdgcn_s_sleep(0);
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+    }
     pow_static_for<0, O::STEPS>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         if constexpr (O::exists(g)) {
             const PowOpRegs me = O::template op<g, true>(job, r);
             constexpr int g1 = O::next(g), g2 = O::next(g1);
-            constexpr int uop = S::kCount > 0 ? O::uop_index(FILL, g1) : -1;
+            constexpr int uop = S::kCount > 0 ? pow_uop_index<O>(FILL, g1) : -1;
+            constexpr bool kslot = g1 >= 0 && O::k_slot(g1);
 #if defined(__HIP_DEVICE_COMPILE__)
             const PowOpRegs n1 = O::template op<g1, false>(job, r), n2 = O::template op<g2, false>(job, r);
             // An asm result must not be read by the very next instruction (s_nop), and the nonce word is live
@@ -550,14 +640,21 @@ __host__ __device__ __forceinline__ void pow_sched_pinned(const PowJobDev& job, 
             else asm volatile("" ::"v"(*me.out));
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (O::fill_before(FILL, g1)) {
-                if constexpr (uop >= 0 && uop < S::kCount) sc.template uop<uop>(job, r);
+                if constexpr (kslot) {
+                    // K, or the scalar sum that stands for K and W's uniform part, of the h + K + W after g1: one
+                    // SALU instruction in the filler's place
+                    uint32_t k = sc.template kx<O::round_of(kslot ? O::next(g1) : 0)>(job);
+                    asm volatile("" : "+s"(k));
+                    r.kx = k;
+                } else if constexpr (uop >= 0 && S::has(uop)) sc.template uop<uop>(job, r);
                 else __builtin_amdgcn_s_sleep(0);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #else
             (void)me;
             (void)g2;
-            if constexpr (uop >= 0 && uop < S::kCount) sc.template uop<uop>(job, r);
+            if constexpr (kslot) r.kx = sc.template kx<O::round_of(kslot ? O::next(g1) : 0)>(job);
+            else if constexpr (uop >= 0 && S::has(uop)) sc.template uop<uop>(job, r);
 #endif
         }
     });
@@ -594,8 +691,22 @@ __host__ __device__ __forceinline__ uint32_t pow_u_bsig1(uint32_t x) { const uin
 // loop then only reads. On the device every step sits between two empty asm statements that redefine the
 // program's registers: they hold the step's place among the pinned instructions, keep the values in SGPRs and
 // hide from the compiler that a shift pair is a rotate, which it would select as v_alignbit_b32, back on the VALU.
-struct PowSplitScalar {
-    static constexpr int kCount = 57;
+// G11 (variant 11): the pinned part starts two rounds earlier, so the steps run from round 12 on; steps 34 and 45
+// keep the next iteration's ce + sv and ca + sv (es, as: a11 and e11 are these plus lanep); three more steps make
+// the uniform parts of W24 and of the first adds of W26 and W33 (PowSchedRegs::us) at the head of the round that
+// reads them; and kx<I> is the SALU instruction in front of round I's h + K + W.
+template <bool G11>
+struct PowSplitScalarT {
+    // G11: the first slots of rounds 22, 24 and 31, in which W24, W26 and W33 are made
+    static constexpr int kW24 = G11 ? PowUopTable<PowFillOrder>::k.first[22] : 57;
+    static constexpr int kW26 = G11 ? PowUopTable<PowFillOrder>::k.first[24] : 58;
+    static constexpr int kW33 = G11 ? PowUopTable<PowFillOrder>::k.first[31] : 59;
+    static_assert(kW24 >= 57 && kW26 > kW24 && kW33 > kW26, "after the sigma halves and the next round 11");
+    static constexpr int kCount = G11 ? kW33 + 1 : 57;
+    static constexpr bool has(int n) { return n < 57 || (G11 && (n == kW24 || n == kW26 || n == kW33)); }
+    uint32_t es, as;         // G11: ce + sv and ca + sv of the coming iteration
+    uint32_t k63;            // G11: round 63's K; the range-form kernel has the range check's base in it
+    uint32_t k17w, c33;      // G11: PowFillDev's
     uint32_t sv;             // this iteration's vb + U
     uint32_t m, glo, bclo;   // 2^p - 1, g & m, b & c & m (round 11's g, b, c)
     uint32_t x1, x0, se, sa; // round 11: Sigma1(e_lo), Sigma0(a_lo), he + Ch_lo, hk[0] + Ch_lo + Maj_lo
@@ -610,12 +721,31 @@ struct PowSplitScalar {
         x0 = pow_u_bsig0(alo);
         se = chlo + job.he;
         sa = chlo + mjlo + job.hk[0];
+        if (G11) {
+            es = at + job.ce;
+            as = at + job.ca;
+        }
+    }
+
+    template <int I>
+    __host__ __device__ __forceinline__ uint32_t kx(const PowJobDev& job) const {
+        if constexpr (I == 17) return sv + k17w;
+        else if constexpr (I == 63) return k63;
+        else return kSha256K[I];
     }
 
     template <int N>
     __host__ __device__ __forceinline__ void uop(const PowJobDev& job, PowSchedRegs& r) {
-        static_assert(N >= 0 && N < kCount, "no such step");
+        static_assert(N >= 0 && N < kCount && has(N), "no such step");
         uint32_t(&xs)[5] = r.xs;
+        if constexpr (N >= 57) {  // on their own: one SGPR each, made where it is read
+            constexpr int n = N == kW24 ? 0 : N == kW26 ? 1 : 2;
+            r.us[n] = sv + (n == 0 ? job.c24 : n == 1 ? job.kw[26] : c33);
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+s"(r.us[n]));
+#endif
+            return;
+        }
 #if defined(__HIP_DEVICE_COMPILE__)
         asm volatile("" : "+s"(a), "+s"(b), "+s"(t), "+s"(l), "+s"(pp), "+s"(sv));
 #endif
@@ -643,6 +773,8 @@ struct PowSplitScalar {
         U_SIG0(28, 4)
         // the next iteration's round 11
         else if constexpr (N == 33) t = sv + 1u;
+        else if constexpr (N == 34 && G11) es = t + job.ce;
+        else if constexpr (N == 35 && G11) l = es & m;
         else if constexpr (N == 34) l = t + job.ce;
         else if constexpr (N == 35) l &= m;
         else if constexpr (N == 36) pp = U_PAIR(l);
@@ -654,6 +786,8 @@ struct PowSplitScalar {
         else if constexpr (N == 42) a = l & job.fxg;
         else if constexpr (N == 43) a ^= glo;  // Ch_lo
         else if constexpr (N == 44) se = a + job.he;
+        else if constexpr (N == 45 && G11) as = t + job.ca;
+        else if constexpr (N == 46 && G11) l = as & m;
         else if constexpr (N == 45) l = t + job.ca;
         else if constexpr (N == 46) l &= m;
         else if constexpr (N == 47) pp = U_PAIR(l);
@@ -669,16 +803,28 @@ struct PowSplitScalar {
 #undef U_SIG1
 #undef U_SIG0
 #if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+s"(a), "+s"(b), "+s"(t), "+s"(l), "+s"(pp), "+s"(x1), "+s"(x0), "+s"(se), "+s"(sa),
-                          "+s"(xs[0]), "+s"(xs[1]), "+s"(xs[2]), "+s"(xs[3]), "+s"(xs[4]));
+        if constexpr (G11) {
+            // only what the step wrote: an xs that is not made yet stays out of the SGPRs
+            asm volatile("" : "+s"(a), "+s"(b), "+s"(t), "+s"(l), "+s"(pp), "+s"(x1), "+s"(x0), "+s"(se), "+s"(sa));
+            constexpr int k = N == 7 ? 1 : N == 12 ? 2 : N == 19 ? 0 : N == 27 ? 3 : N == 32 ? 4 : -1;
+            if constexpr (k >= 0) asm volatile("" : "+s"(xs[k]));
+            if constexpr (N == 34) asm volatile("" : "+s"(es));
+            if constexpr (N == 45) asm volatile("" : "+s"(as));
+        } else {
+            asm volatile("" : "+s"(a), "+s"(b), "+s"(t), "+s"(l), "+s"(pp), "+s"(x1), "+s"(x0), "+s"(se), "+s"(sa),
+                              "+s"(xs[0]), "+s"(xs[1]), "+s"(xs[2]), "+s"(xs[3]), "+s"(xs[4]));
+        }
 #endif
     }
 };
-struct PowSplitCache {
+using PowSplitScalar = PowSplitScalarT<false>;
+template <bool G11>
+struct PowSplitCacheT {
     PowSplitKeys key;   // s >> p of the five sums, which the lane constants were computed from
     uint32_t next;      // the first vb + U at which one of them is another
-    PowSplitScalar sc;  // the scalar program's registers; x1, x0, se, sa are those of the coming iteration
+    PowSplitScalarT<G11> sc;  // the scalar program's registers; x1, x0, se, sa are those of the coming iteration
 };
+using PowSplitCache = PowSplitCacheT<false>;
 
 // sv = vb + U
 __host__ __device__ __forceinline__ PowSplitKeys pow_split_sums(const PowJobDev& job, uint32_t sv) {
@@ -688,8 +834,9 @@ __host__ __device__ __forceinline__ PowSplitKeys pow_split_sums(const PowJobDev&
 // At sv: the lane constants whose key differs from the cached one (all: every one, for the prologue), and the next
 // sv at which a key changes. A sum's s >> p changes when its low p bits wrap, so the first of the five to do so is
 // the one with the largest low part: 2^p minus that many steps from here.
+template <class Cache>
 __host__ __device__ __forceinline__ void pow_split_lane_update(const PowJobDev& job, uint32_t p, uint32_t sv, uint32_t lane,
-                                                               PowSplitCache& cached, PowSplitLane& lc, bool all) {
+                                                               Cache& cached, PowSplitLane& lc, bool all) {
     const uint32_t m = (1u << p) - 1u, hm = ~m;
     const PowSplitKeys s = pow_split_sums(job, sv);
     const PowSplitKeys key = {s.v >> p, s.e >> p, s.a >> p, s.w17 >> p, s.w24 >> p};
@@ -724,11 +871,12 @@ __host__ __device__ __forceinline__ void pow_split_lane_update(const PowJobDev& 
 }
 
 // Before a wave's first iteration, whose sv is vb + U
+template <class Cache>
 __host__ __device__ __forceinline__ void pow_split_prologue(const PowJobDev& job, uint32_t p, uint32_t sv, uint32_t lane,
-                                                            PowSplitCache& cached, PowSplitLane& lc) {
+                                                            Cache& cached, PowSplitLane& lc) {
     lc.lanep = lane << p;
     pow_split_lane_update(job, p, sv, lane, cached, lc, true);
-    PowSplitScalar& sc = cached.sc;
+    auto& sc = cached.sc;
     sc = {};
     sc.m = (1u << p) - 1u;
     sc.glo = job.st[5] & sc.m;
@@ -767,13 +915,57 @@ __host__ __device__ __forceinline__ uint32_t pow_a_split(const PowJobDev& job, u
     return r.s[(0 - 64) & 7];
 }
 
-// One nonce word through the split function (the tests' H0 of variant 10): the word as lane << 26 | U
+// Variant 11: variant 10 with one scalar or sequencer instruction in front of every rotate and add3 and nothing else
+// between VALU instructions. Rounds 12 and 13 are pinned too; each K is loaded in the slot in front of its own
+// h + K + W and is dead after it; the nonce word and W17 are not materialised (their readers take an SGPR sum plus
+// lanep). Returns a after round 63; range: a + range_base, which round 63 adds with its K.
+template <int FILL>
+__host__ __device__ __forceinline__ uint32_t pow_a_fill(const PowJobDev& job, uint32_t p, uint32_t sv, uint32_t lane,
+                                                        PowSplitCacheT<true>& cached, PowSplitLane& lc,
+                                                        const PowFillDev& fx, bool range) {
+    using O = PowFillOrder;
+    using S = PowSplitScalarT<true>;
+    static_assert(PowUopTable<O>::k.first[63] + O::kUopsPerRound > S::kCount, "a filler's place for every step");
+    if (sv == cached.next) {
+        pow_split_lane_update(job, p, sv, lane, cached, lc, false);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // the maximum of the five low parts comes from v_max3_u32: back to an SGPR here, off the hot path, so that
+        // the test above is a scalar compare
+        cached.next = __builtin_amdgcn_readfirstlane(cached.next);
+#endif
+    }
+    S& sc = cached.sc;
+    sc.sv = sv;
+    sc.k63 = range ? fx.k63r : kSha256K[63];
+    sc.k17w = fx.k17w;
+    sc.c33 = fx.c33;
+    PowSchedRegs r = {};
+#pragma unroll
+    for (int k = 0; k < 5; ++k) r.xl[k] = lc.xl[k];
+    r.lanep = lc.lanep;
+    {
+        // round 11 from the halves, as in pow_a_split; a11 and e11 from the sums the last iteration left
+        const uint32_t x1 = sc.x1 ^ lc.s1, x0 = sc.x0 ^ lc.s0;
+        uint32_t(&s)[8] = r.s;
+        constexpr int i = O::R0 + 1;
+        s[(0 - i) & 7] = sc.as + lc.lanep; s[(1 - i) & 7] = job.st[0]; s[(2 - i) & 7] = job.st[1];
+        s[(4 - i) & 7] = sc.es + lc.lanep; s[(5 - i) & 7] = job.st[4]; s[(6 - i) & 7] = job.st[5];
+        s[(3 - i) & 7] = x1 + lc.ch + sc.se;           // e12 = d + t1
+        s[(7 - i) & 7] = (x1 + x0 + lc.cm) + sc.sa;  // a12 = t1 + t2
+    }
+    pow_sched_pinned<O, FILL>(job, r, sc);
+    return r.s[(0 - 64) & 7];
+}
+
+// One nonce word through the split function (the tests' H0 of variants 10 and 11): the word as lane << 26 | U
+template <bool G11 = false>
 __host__ __device__ __forceinline__ uint32_t pow_h0_split(const PowJobDev& job, uint32_t v) {
     const uint32_t p = 26, lane = v >> p, sv = v & ((1u << p) - 1u);
-    PowSplitCache cached;
+    PowSplitCacheT<G11> cached;
     PowSplitLane lc;
     pow_split_prologue(job, p, sv, lane, cached, lc);
-    return job.mid[0] + pow_a_split<2>(job, p, sv, lane, cached, lc);
+    if constexpr (G11) return job.mid[0] + pow_a_fill<2>(job, p, sv, lane, cached, lc, make_pow_fill(job), false);
+    else return job.mid[0] + pow_a_split<2>(job, p, sv, lane, cached, lc);
 }
 
 
@@ -873,6 +1065,47 @@ __global__ __launch_bounds__(256, MIN_WAVES_PER_SIMD) void pow_search_sched_kern
 // Variant 10. One dispatch covers U in [u_begin, u_end) of the piece v = vb + U + (lane << p): wave w of the grid
 // (four per block) takes the `iters` values from u_begin + w * iters on, cut at u_end. The host keeps
 // (waves + 3) * iters below 2^32. RANGE: the job's hit predicate is the one range check (PowJobDev::range_ok).
+// Variant 11, the same dispatch as variant 10 (pow_search_split_kernel below). RANGE: round 63's K carries
+// range_base, so the loop ends in the compare; a wave with no hit takes one branch over the cold block.
+// __launch_bounds__(256, 7): the compiler's SGPR budget for 8 waves/SIMD is 80 and makes it spill to VGPR lanes and
+// reload in the loop; for 7 it is 96, of which the kernel takes 90, and with those and its 43 VGPRs it still runs
+// 8 waves/SIMD.
+template <bool RANGE>
+__global__ __launch_bounds__(256, 7) void pow_search_fill_kernel(PowJobDev job, uint32_t vb, uint32_t p, uint32_t u_begin,
+                                                                 uint32_t u_end, uint32_t iters,
+                                                                 uint32_t* __restrict__ out_count,
+                                                                 uint32_t* __restrict__ out_words, uint32_t cap,
+                                                                 PowFillDev fx) {
+    const uint32_t wave = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t u = u_begin + wave * iters;
+    if (u >= u_end) return;
+    const uint32_t u_stop = u_end - u < iters ? u_end : u + iters;
+    PowSplitCacheT<true> cached;
+    PowSplitLane lc;
+    pow_split_prologue(job, p, vb + u, lane, cached, lc);
+    cached.next = __builtin_amdgcn_readfirstlane(cached.next);  // see pow_a_fill
+    for (; u < u_stop; ++u) {
+        const uint32_t sv = vb + u;
+        const uint32_t a = pow_a_fill<2>(job, p, sv, lane, cached, lc, fx, RANGE);
+        bool hit;
+        if (RANGE) {
+            hit = a < job.range_width;
+        } else {
+            const uint32_t h0 = job.mid[0] + a;
+            hit = ((h0 ^ job.tword) & job.tmask) == 0 && ((h0 >> job.frac_shift) & 0xfu) < job.frac_limit;
+        }
+#if defined(__HIP_DEVICE_COMPILE__)
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit) != 0, 0)) {
+            if (hit) {
+                const uint32_t slot = atomicAdd(out_count, 1u);
+                if (slot < cap) out_words[slot] = sv + lc.lanep;
+            }
+        }
+#endif
+    }
+}
+
 template <bool RANGE>
 __global__ __launch_bounds__(256, 8) void pow_search_split_kernel(PowJobDev job, uint32_t vb, uint32_t p, uint32_t u_begin,
                                                                   uint32_t u_end, uint32_t iters,
@@ -1024,19 +1257,42 @@ bool pow_range_hit_host(const PowJobHost& hj, uint32_t h0) {
     return a + j.range_base < j.range_width;
 }
 
-std::vector<uint32_t> pow_split_wave_host(const PowJobHost& hj, uint32_t vb, uint32_t p, uint32_t u_first,
-                                          uint32_t iters) {
-    if (hj.header.size() != 108) throw std::invalid_argument("the split kernel is for the 108-byte header");
-    if (p > uint32_t(kPowSplitMaxLog2)) throw std::invalid_argument("p must be at most 26: the lane index takes six bits");
-    const PowJobDev job = make_pow_job(hj);
-    PowSplitCache cached[64];
+template <bool G11>
+static std::vector<uint32_t> pow_split_wave_loop(const PowJobDev& job, uint32_t vb, uint32_t p, uint32_t u_first,
+                                                 uint32_t iters) {
+    PowSplitCacheT<G11> cached[64];
     PowSplitLane lc[64];
+    const PowFillDev fx = make_pow_fill(job);
+    (void)fx;
     for (uint32_t lane = 0; lane < 64; ++lane) pow_split_prologue(job, p, vb + u_first, lane, cached[lane], lc[lane]);
     std::vector<uint32_t> out(size_t(iters) * 64);
     for (uint32_t it = 0; it < iters; ++it)
-        for (uint32_t lane = 0; lane < 64; ++lane)
-            out[size_t(it) * 64 + lane] = job.mid[0] + pow_a_split<2>(job, p, vb + u_first + it, lane, cached[lane], lc[lane]);
+        for (uint32_t lane = 0; lane < 64; ++lane) {
+            const uint32_t sv = vb + u_first + it;
+            if constexpr (G11) out[size_t(it) * 64 + lane] = job.mid[0] + pow_a_fill<2>(job, p, sv, lane, cached[lane], lc[lane], fx, false);
+            else out[size_t(it) * 64 + lane] = job.mid[0] + pow_a_split<2>(job, p, sv, lane, cached[lane], lc[lane]);
+        }
     return out;
+}
+
+std::vector<uint32_t> pow_split_wave_host(const PowJobHost& hj, uint32_t vb, uint32_t p, uint32_t u_first,
+                                          uint32_t iters, int variant) {
+    if (hj.header.size() != 108) throw std::invalid_argument("the split kernel is for the 108-byte header");
+    if (p > uint32_t(kPowSplitMaxLog2)) throw std::invalid_argument("p must be at most 26: the lane index takes six bits");
+    if (variant == 0) variant = 11;  // kPowDefaultVariant, checked below
+    if (variant != 10 && variant != 11) throw std::invalid_argument("the wave loop is variant 10's and variant 11's");
+    const PowJobDev job = make_pow_job(hj);
+    return variant == 11 ? pow_split_wave_loop<true>(job, vb, p, u_first, iters)
+                         : pow_split_wave_loop<false>(job, vb, p, u_first, iters);
+}
+
+// the range-form compare of variant 11's kernel on a digest word: a' = a + range_base comes out of round 63
+bool pow_range_hit_folded_host(const PowJobHost& hj, uint32_t h0) {
+    const PowJobDev j = make_pow_job(hj);
+    if (!j.range_ok) throw std::invalid_argument("this job's predicate has no range form");
+    const uint32_t a = h0 - j.mid[0];                     // a after round 63 with the plain K[63]
+    const uint32_t folded = a - kSha256K[63] + make_pow_fill(j).k63r;    // the same round with k63r in K[63]'s place
+    return folded < j.range_width;
 }
 
 // H0 of SHA256(header with nonce word v) through pow_h0_pre on the host: the kernel's arithmetic on the
@@ -1084,9 +1340,15 @@ static PowDeviceBuffers& pow_buffers(uint32_t cap) {
 //     Pieces of 2^14..2^32 words; what is left of a range below 2^14 words runs on variant 9's kernel
 //  0  the default, kPowDefaultVariant
 // v1 headers have the original loop (1-3) and the precomputed one (4 and up) only.
-constexpr int kPowDefaultVariant = 10;
+//  11  variant 10 with one scalar or sequencer instruction in front of every slow instruction (pow_a_fill,
+//     pow_search_fill_kernel): each K loaded in the slot in front of its add3, rounds 12 and 13 pinned, the nonce
+//     word and W17 not materialised, the range check's base folded into round 63's K
+constexpr int kPowDefaultVariant = 11;
 constexpr int kPowSplitVariant = 10;
-constexpr int kPowVariantCount = 11;
+constexpr int kPowFillVariant = 11;
+constexpr int kPowVariantCount = 12;
+static_assert(kPowDefaultVariant == 11, "pow_split_wave_host resolves 0 to the default variant by its number");
+static bool pow_is_split(int variant) { return variant == kPowSplitVariant || variant == kPowFillVariant; }
 
 using PowKernelFn = void (*)(PowJobDev, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t);
 
@@ -1098,7 +1360,7 @@ static int pow_resolve_variant(int variant) {
 // The grid-strided kernel of a variant; for variant 10 the one that runs what its pieces leave over
 static PowKernelFn pow_kernel_fn(bool v2, int variant) {
     variant = pow_resolve_variant(variant);
-    if (v2 && variant == kPowSplitVariant) variant = 9;
+    if (v2 && pow_is_split(variant)) variant = 9;
     // v1 at 7 waves/SIMD: left to itself the compiler takes 106 SGPRs and spills some to VGPR lanes in the loop
     if (!v2) return variant >= 4 ? &pow_search_pre_kernel<1, 7> : &pow_search_kernel<1, 1>;
     switch (variant) {
@@ -1127,7 +1389,8 @@ uint32_t pow_job_h0_host(const PowJobHost& hj, uint32_t v, int variant) {
         case 7: return pow_h0_sched<2, 2, false, 0>(job, v);
         case 8: return pow_h0_sched<2, 2, false, 1>(job, v);
         case 9: return pow_h0_sched<2, 2, false, 2>(job, v);
-        case 10: return pow_h0_split(job, v);
+        case 10: return pow_h0_split<false>(job, v);
+        case 11: return pow_h0_split<true>(job, v);
         default: return pow_h0_pre<2>(job, v);
     }
 }
@@ -1138,9 +1401,10 @@ static int pow_resident_blocks(bool v2, int variant) {
     int dev = 0, cus = 0, per_cu = 0;
     hip_check(hipGetDevice(&dev), "hipGetDevice");
     hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "attr");
-    const void* fn = v2 && pow_resolve_variant(variant) == kPowSplitVariant
-                         ? reinterpret_cast<const void*>(&pow_search_split_kernel<true>)
-                         : reinterpret_cast<const void*>(pow_kernel_fn(v2, variant));
+    const int rv = pow_resolve_variant(variant);
+    const void* fn = v2 && rv == kPowFillVariant    ? reinterpret_cast<const void*>(&pow_search_fill_kernel<true>)
+                     : v2 && rv == kPowSplitVariant ? reinterpret_cast<const void*>(&pow_search_split_kernel<true>)
+                                                    : reinterpret_cast<const void*>(pow_kernel_fn(v2, variant));
     hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0), "occupancy");
     if (per_cu < 1) per_cu = 1;
     if (per_cu > 8) per_cu = 8;
@@ -1180,11 +1444,14 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
         chunk_iters = uint32_t(std::max<uint64_t>(1, (uint64_t(1) << lg) / per_launch_threads));
     }
     uint64_t done = 0;
-    if (v2 && pow_resolve_variant(variant) == kPowSplitVariant) {
+    if (v2 && pow_is_split(pow_resolve_variant(variant))) {
         // Maximal power-of-two pieces, largest first; grid_blocks and chunk_iters keep their meaning: blocks per
         // dispatch and iterations (values of U) per wave per dispatch. A piece smaller than a dispatch is spread
         // over as many waves as it has iterations for.
+        const bool fill = pow_resolve_variant(variant) == kPowFillVariant;
         const auto split = job.range_ok ? &pow_search_split_kernel<true> : &pow_search_split_kernel<false>;
+        const auto filled = job.range_ok ? &pow_search_fill_kernel<true> : &pow_search_fill_kernel<false>;
+        const PowFillDev fx = make_pow_fill(job);
         const uint64_t waves = uint64_t(grid_blocks) * (block / 64);
         while (count - done >= (uint64_t(1) << (kPowSplitMinLog2 + 6))) {
             int lg = 63 - __builtin_clzll(count - done);
@@ -1196,8 +1463,12 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
                 const uint64_t need = (uint64_t(left) + iters - 1) / iters;  // waves that have an iteration
                 const uint32_t gb = uint32_t(std::min<uint64_t>(uint64_t(grid_blocks), (need + 3) / 4));
                 const uint32_t u_end = uint32_t(std::min<uint64_t>(n_u, u + uint64_t(gb) * 4 * iters));
-                hipLaunchKernelGGL(split, dim3(gb), dim3(block), 0, st, job, vb, p, u, u_end, iters, buf.d_count,
-                                   buf.d_words, cap);
+                if (fill)
+                    hipLaunchKernelGGL(filled, dim3(gb), dim3(block), 0, st, job, vb, p, u, u_end, iters, buf.d_count,
+                                       buf.d_words, cap, fx);
+                else
+                    hipLaunchKernelGGL(split, dim3(gb), dim3(block), 0, st, job, vb, p, u, u_end, iters, buf.d_count,
+                                       buf.d_words, cap);
                 hip_check(hipGetLastError(), "pow_search_split_kernel launch");
                 u = u_end;
             }

@@ -12,6 +12,11 @@ schedule words W16..W63 with every nonce-independent term folded):
                             t1 = add3(h, S1, Ch) + add3(t1, K+W)   e = d + t1   a = add3(t1, S0, Maj)
     per schedule word        s0, s1: 2 rotates + shift + XOR3 each; W = add3 + add
 
+For each loop it also prints how the two slow opcodes (v_alignbit_b32, v_add3_u32) are issued: a histogram of the
+number of non-VALU instructions (s_sleep, s_nop, SALU) between a slow instruction and the VALU instruction before
+it (0 / 1 / 2 or more: one is the cheapest, docs/PERF.md "PoW scalar slots"), and the s_mov_b32 and v_readlane_b32
+counts of the audited path.
+
 Usage: python scripts/pow_isa_audit.py [--out profiles/r6/pow_isa_r6.txt]
 """
 import argparse
@@ -39,9 +44,24 @@ def compile_asm() -> str:
 
 
 HIT_TEST = r's_cbranch_exec(n)?z'
+HIT_TEST_WAVE = r's_cbranch_vccn?z'  # variant 11: one branch per wave, taken when any lane has a hit
+SLOW = r'^v_alignbit_b32|^v_add3_u32'
 
 
-def cheapest_path(loop: str) -> list:
+def fill_histogram(ins) -> dict:
+    """{0, 1, 2: slow instructions with that many (2: two or more) non-VALU instructions directly in front}."""
+    hist, gap = {0: 0, 1: 0, 2: 0}, 0
+    for i in ins:
+        if i.startswith('v_'):
+            if re.match(SLOW, i):
+                hist[min(gap, 2)] += 1
+            gap = 0
+        else:
+            gap += 1
+    return hist
+
+
+def cheapest_path(loop: str, hit_test: str = HIT_TEST) -> list:
     """The instructions of one iteration that takes no optional work: the loop cut into basic blocks, and from
     the header to the block that ends in the hit test the path with the fewest VALU instructions. A loop of one
     block is that block. The split kernel (variant 10) recomputes lane constants in blocks of their own when a
@@ -59,7 +79,7 @@ def cheapest_path(loop: str) -> list:
         blocks[-1].append(ln.split())
         if re.match(r's_cbranch|s_branch', ln.split()[0]):
             blocks.append([])
-    last = next((i for i, b in enumerate(blocks) if b and re.match(HIT_TEST, b[-1][0])), len(blocks) - 1)
+    last = max((i for i, b in enumerate(blocks) if b and re.match(hit_test, b[-1][0])), default=len(blocks) - 1)
     cost = lambda b: (sum(1 for t in b if t[0].startswith('v_')), len(b))
     best = {0: (cost(blocks[0]), [0])}
     todo = [0]
@@ -80,7 +100,7 @@ def cheapest_path(loop: str) -> list:
                 todo.append(j)
     path = best.get(last, (None, list(range(last + 1))))[1]
     ins = [t[0] for i in path for t in blocks[i]]
-    return ins[:-1] if ins and re.match(HIT_TEST, ins[-1]) else ins
+    return ins[:-1] if ins and re.match(hit_test, ins[-1]) else ins
 
 
 def loop_bodies(asm: str) -> dict:
@@ -99,8 +119,12 @@ def loop_bodies(asm: str) -> dict:
             continue
         loop = body[hdr.end():]
         stop = re.search(HIT_TEST, loop)  # the hit test: everything before it runs once per nonce
+        back = re.search(r's_cbranch_\w+\s+' + re.escape(hdr.group(1)) + r'\b', loop)
+        wave = [m for m in re.finditer(HIT_TEST_WAVE, loop[:back.start()] if back else '')]
+        if wave and not (stop and back and stop.start() < back.start()):
+            stop = wave[-1]  # the hit test is the last branch on vcc before the back edge
         loop = loop[:stop.end()] if stop else loop
-        ins = cheapest_path(loop)
+        ins = cheapest_path(loop, stop.group(0) if stop else HIT_TEST)
         out[name] = (ins, int(vg.group(1)) if vg else None, int(occ.group(1)) if occ else None)
         del tail
     return out
@@ -141,6 +165,12 @@ def main():
             if v:
                 lines.append(f'    {k:28s} {v:5d}')
         lines.append(f'    {"VALU per nonce":28s} {valu:5d}')
+        if any(i.startswith(('s_sleep', 's_nop')) for i in ins):
+            h = fill_histogram(ins)
+            lines.append(f'    slow opcodes by non-VALU instructions in front   0: {h[0]}   1: {h[1]}   2+: {h[2]}')
+            lines.append(f'    s_mov_b32 {sum(i == "s_mov_b32" for i in ins)}   '
+                         f'v_readlane_b32 {sum(i == "v_readlane_b32" for i in ins)}   '
+                         f's_nop {sum(i == "s_nop" for i in ins)}')
         lines.append('')
     f = floor_v2()
     lines.append(f'hand-derived floor of the v2 formulation: {f["total"]} VALU per nonce '
