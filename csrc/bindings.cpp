@@ -690,6 +690,59 @@ PYBIND11_MODULE(_native, m) {
         { py::gil_scoped_release rel; utxo_records_digest_host(p, pp, n, threads, r); }
         return digest_out(r);
     }, py::arg("recs"), py::arg("payload") = py::none(), py::arg("threads") = 1);
+    // UTXO proofs (native.h): a Merkle snapshot of a table's entries with a tag in tag_mask, or of records n x 40 with
+    // payloads n x 80 (None: no payload) built on the GPU / on host threads; info and proofs by snapshot id
+    m.def("utxo_merkle_build", [](int64_t h, uint32_t tag_mask, uint32_t launch_lever) {
+        py::gil_scoped_release rel;
+        return utxo_merkle_build(h, tag_mask, launch_lever);
+    }, py::arg("h"), py::arg("tag_mask") = 0x7fu, py::arg("launch_lever") = 0u);
+    m.def("utxo_merkle_build_records", [digest_args](py::buffer recs, py::object payload, uint32_t launch_lever) {
+        py::buffer_info pi;
+        int64_t n; const uint8_t* pp;
+        const uint8_t* p = digest_args(recs, payload, pi, n, pp);
+        py::gil_scoped_release rel;
+        return utxo_merkle_build_records(p, pp, n, launch_lever);
+    }, py::arg("recs"), py::arg("payload") = py::none(), py::arg("launch_lever") = 0u);
+    m.def("utxo_merkle_build_records_host", [digest_args](py::buffer recs, py::object payload, int threads) {
+        py::buffer_info pi;
+        int64_t n; const uint8_t* pp;
+        const uint8_t* p = digest_args(recs, payload, pi, n, pp);
+        py::gil_scoped_release rel;
+        return utxo_merkle_build_records_host(p, pp, n, threads);
+    }, py::arg("recs"), py::arg("payload") = py::none(), py::arg("threads") = 1);
+    m.def("utxo_merkle_info", [](int64_t id) {
+        const MerkleInfo r = utxo_merkle_info(id);
+        py::dict d;
+        d["root"] = py::bytes(reinterpret_cast<const char*>(r.root), 32);
+        d["count"] = r.count;
+        d["levels"] = r.levels;
+        d["bytes"] = r.bytes;
+        d["on_device"] = r.on_device;
+        return d;
+    });
+    // (present u8[q], first u32[q + 1], position u32[m], entry slots bytes[112 m], path_first u32[m + 1], path bytes)
+    m.def("utxo_merkle_prove", [recs_arg](int64_t id, py::buffer recs) {
+        int64_t q;
+        const uint8_t* p = recs_arg(recs, q);
+        MerkleProveOut r;
+        { py::gil_scoped_release rel; utxo_merkle_prove(id, p, q, r); }
+        auto u32 = [](const std::vector<uint32_t>& v) {
+            py::array_t<uint32_t> a(py::ssize_t(v.size()));
+            if (!v.empty()) std::memcpy(a.mutable_data(), v.data(), 4 * v.size());
+            return a;
+        };
+        py::array_t<uint8_t> present(py::ssize_t(r.present.size()));
+        if (!r.present.empty()) std::memcpy(present.mutable_data(), r.present.data(), r.present.size());
+        return py::make_tuple(present, u32(r.first), u32(r.position),
+                              py::bytes(reinterpret_cast<const char*>(r.entry.data()), r.entry.size()), u32(r.path_first),
+                              py::bytes(reinterpret_cast<const char*>(r.path.data()), r.path.size()));
+    });
+    m.def("utxo_merkle_free", [](int64_t id) { py::gil_scoped_release rel; utxo_merkle_free(id); });
+    m.def("utxo_merkle_held", []() {
+        uint64_t n = 0, b = 0;
+        utxo_merkle_held(&n, &b);
+        return py::make_tuple(n, b);
+    });
     // UTXO diff (native.h): (status u8[n], extra records, extra payloads, extra, repeated, live, wait s, hold s)
     m.def("utxo_diff", [digest_args](int64_t h, py::buffer recs, py::object payload, uint32_t tag_mask, uint32_t limit,
                                      uint32_t chunk_records) {

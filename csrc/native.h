@@ -223,6 +223,52 @@ void utxo_records_digest(const uint8_t* recs, const uint8_t* pay_or_null, int64_
 void utxo_records_digest_host(const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, int threads,
                               StateDigestOut& out);
 
+// ---------------------------------------------------------------- UTXO proofs: utxo_merkle.hip, utxo_merkle_host.cpp
+// A Merkle tree over a set of entries, so that one entry can be checked against 32 bytes and a count.
+//   entry   E as the state digest defines it above (44, 77 or 108 bytes)
+//   order   ascending by E's first 34 bytes: txid as 32 bytes, then u8(index), then u8(tag). Outpoints are unique in
+//           a healthy index; the tag only makes the order total.
+//   tree    RFC 6962 / RFC 9162 2.1.1: leaf = SHA-256(0x00 | E), node = SHA-256(0x01 | left | right), the tree of n
+//           leaves split at the largest power of two below n; the root of the empty set is SHA-256 of the empty
+//           string. Both builders go level by level instead: neighbours are paired and an unpaired last node is
+//           promoted unchanged, which gives the same tree (the left subtree of every split is complete).
+//   commitment  (root, count): a verifier needs both.
+//   leaf proof  the leaf's position, its E and the RFC 9162 2.1.3 audit path, bottom up (a promoted node adds none).
+//   outpoint proof (txid, index)  present: the leaf proofs of every leaf with that outpoint (normally one); absent:
+//           those of the predecessor and the successor in the order (adjacent positions whose keys bracket the
+//           query; one of the two when the query sorts before the first or after the last leaf, none for the empty
+//           set).
+// A snapshot is built from one state (utxo_merkle_build: the entries of table h whose tag's bit is set in tag_mask,
+// tags above 31 never, collected under ONE hold of the table lock behind any queued async apply) and then owns its
+// buffers: it answers without the table lock until it is freed. It holds, per entry, a 112-byte slot (E, zeros up
+// to byte 108, then u32le(length of E)) and every level's 32-byte nodes: about 176 bytes. _build_records builds from
+// n host records (40 bytes) and payloads (80 bytes, nullptr: none) on the GPU, _build_records_host on `threads` host
+// threads with the same result whatever their number. launch_lever (0: 256 items per block; else 1..256, the items
+// a 256-thread block takes, so that tiny inputs cross block boundaries in the leaf and level kernels) is a test
+// lever, not set by the node.
+constexpr size_t kMerkleSlot = 112;
+struct MerkleInfo {
+    uint8_t root[32];
+    uint64_t count = 0, bytes = 0;  // bytes: what the snapshot holds (device or host)
+    uint32_t levels = 0;            // stored levels, the leaves' included: 0 for the empty set
+    bool on_device = false;
+};
+// Answers to q queries (40-byte records; the tag is ignored): query i is present[i] and owns the leaf proofs
+// [first[i], first[i + 1]); leaf proof j is position[j], the slot entry[112 j ..] and the sibling hashes
+// path[32 path_first[j] .. 32 path_first[j + 1]), bottom up.
+struct MerkleProveOut {
+    std::vector<uint8_t> present;
+    std::vector<uint32_t> first, position, path_first;
+    std::vector<uint8_t> entry, path;
+};
+int64_t utxo_merkle_build(int64_t h, uint32_t tag_mask, uint32_t launch_lever);
+int64_t utxo_merkle_build_records(const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, uint32_t launch_lever);
+int64_t utxo_merkle_build_records_host(const uint8_t* recs, const uint8_t* pay_or_null, int64_t n, int threads);
+MerkleInfo utxo_merkle_info(int64_t id);
+void utxo_merkle_prove(int64_t id, const uint8_t* recs, int64_t q, MerkleProveOut& out);
+void utxo_merkle_free(int64_t id);  // an unknown id is ignored
+void utxo_merkle_held(uint64_t* snapshots, uint64_t* bytes);  // over all live snapshots
+
 // ---------------------------------------------------------------- UTXO diff: utxo_diff.hip
 // Which entries differ between table h and n host records (40 bytes) with payloads (80 bytes, nullptr: none), an
 // entry being what the state digest hashes (E above) and the outpoint (txid, index) alone its identity. status[i]

@@ -162,15 +162,15 @@ void utxo_block_inputs(int64_t h, const uint8_t* keys, int64_t n_in, const int32
 // then the txid's four 64-bit big-endian words from least to most significant; the message is gathered on
 // the device and hashed on the host (Merkle–Damgard is sequential).
 
-// column c of the sort: 0 = index, 1..4 = big-endian txid word (4 - c), gathered through perm
+// column c of the sort: 0 = index, 1..4 = big-endian txid word (4 - c), 5 = tag, gathered through perm
 __global__ __launch_bounds__(256) void sort_column_kernel(const UtxoKeyRec* __restrict__ recs,
                                                           const uint32_t* __restrict__ perm, uint32_t n, int c,
                                                           uint64_t* __restrict__ col) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const UtxoKeyRec& r = recs[perm[i]];
-    if (c == 0) {
-        col[i] = r.index & 0xffu;
+    if (c == 0 || c == 5) {
+        col[i] = (c == 0 ? r.index : r.tag) & 0xffu;
         return;
     }
     const uint8_t* b = r.txid + 8 * (4 - c);
@@ -197,28 +197,37 @@ __global__ __launch_bounds__(256) void set_message_kernel(const UtxoKeyRec* __re
     o[32] = uint8_t(r.index);
 }
 
+// The sort (declared in utxo_dev.h: the Merkle build of utxo_merkle.hip orders its leaves with it, the tag as one
+// more least-significant column): the least significant column first; radix sort is stable.
+std::unique_ptr<SortedPerm> sort_records(const UtxoKeyRec* recs, uint32_t n, bool by_tag, hipStream_t st) {
+    size_t temp_bytes = 0;
+    stream_check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, static_cast<uint64_t*>(nullptr),
+                                                    static_cast<uint64_t*>(nullptr), static_cast<uint32_t*>(nullptr),
+                                                    static_cast<uint32_t*>(nullptr), n, 0, 64, st),
+                 "radix sort sizing");
+    auto s = std::make_unique<SortedPerm>(n, temp_bytes);
+    launch(iota_kernel, n, st, "iota_kernel", s->perm_a.p, n);
+    uint32_t* pa = s->perm_a.p;
+    uint32_t* pb = s->perm_b.p;
+    for (int c = by_tag ? -1 : 0; c <= 4; ++c) {
+        const int col = c < 0 ? 5 : c;
+        launch(sort_column_kernel, n, st, "sort_column_kernel", recs, pa, n, col, s->col_a.p);
+        stream_check(hipcub::DeviceRadixSort::SortPairs(s->temp.p, temp_bytes, s->col_a.p, s->col_b.p, pa, pb, n, 0,
+                                                        c <= 0 ? 8 : 64, st),
+                     "radix sort");
+        std::swap(pa, pb);
+    }
+    s->perm = pa;
+    return s;
+}
+
 // The n (> 0) collected records of one table as K12's message, 33 bytes each in (txid, index) order, in a
 // device buffer; sorted and gathered on stream `st`. The sort's scratch goes back to the pool on return, so
 // the call ends with a sync of `st`.
 static PooledBuf<uint8_t> k12_sorted_message(const UtxoKeyRec* recs, uint32_t n, hipStream_t st) {
-    PooledBuf<uint32_t> perm_a(n), perm_b(n);
-    PooledBuf<uint64_t> col_a(n), col_b(n);
-    launch(iota_kernel, n, st, "iota_kernel", perm_a.p, n);
-    size_t temp_bytes = 0;
-    stream_check(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, col_a.p, col_b.p, perm_a.p, perm_b.p, n, 0, 64, st),
-                 "radix sort sizing");
-    PooledBuf<uint8_t> temp(temp_bytes);
-    uint32_t* pa = perm_a.p;
-    uint32_t* pb = perm_b.p;
-    for (int c = 0; c <= 4; ++c) {  // least significant column first; radix sort is stable
-        launch(sort_column_kernel, n, st, "sort_column_kernel", recs, pa, n, c, col_a.p);
-        stream_check(hipcub::DeviceRadixSort::SortPairs(temp.p, temp_bytes, col_a.p, col_b.p, pa, pb, n, 0,
-                                                        c == 0 ? 8 : 64, st),
-                     "radix sort");
-        std::swap(pa, pb);
-    }
+    const std::unique_ptr<SortedPerm> sorted = sort_records(recs, n, false, st);
     PooledBuf<uint8_t> d_msg(size_t(n) * 33);
-    launch(set_message_kernel, n, st, "set_message_kernel", recs, pa, n, d_msg.p);
+    launch(set_message_kernel, n, st, "set_message_kernel", recs, sorted->perm, n, d_msg.p);
     stream_check(hipStreamSynchronize(st), "k12 sort sync");
     return d_msg;
 }

@@ -1,7 +1,8 @@
-// What the UTXO translation units share (utxo_table.hip, utxo_scan.hip, utxo_owners.hip, utxo_block.hip): the
-// slot, key-record and payload layouts, the device helpers on them, the launch helper and the table handle.
-// Private to those files, whose common includes are here too; the design is described at the top of
-// utxo_table.hip, which also defines what is only declared here.
+// What the UTXO translation units share (utxo_table.hip, utxo_scan.hip, utxo_owners.hip, utxo_block.hip,
+// utxo_digest.hip, utxo_diff.hip, utxo_merkle.hip): the slot, key-record and payload layouts, the device helpers on
+// them, the launch helper, the table handle, and the passes one file queues for another (collect() and lookup() of
+// utxo_table.hip, sort_records() of utxo_block.hip). Private to those files, whose common includes are here too; the
+// design is described at the top of utxo_table.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <vector>
@@ -155,5 +157,18 @@ void collect(const UtxoTableDev& t, uint32_t tag, UtxoKeyRec* out, UtxoPayload* 
 // queue utxo_lookup_kernel for the n device-resident records on the node stream: tags_out[i] = tag or 0xff,
 // pay_out[i] = the payload or zeros
 void lookup(const UtxoTableDev& t, const UtxoKeyRec* recs, int64_t n, uint8_t* tags_out, UtxoPayload* pay_out);
+
+// Defined in utxo_block.hip: K12's stable LSD radix sort of n (> 0) device-resident records by (txid as bytes,
+// index), with by_tag by (txid, index, tag), queued on stream `st`. perm[i] is the number of the record that comes
+// i-th. The permutation and the sort's scratch go back to the pool with the object, so its owner synchronises `st`
+// before letting go of it.
+struct SortedPerm {
+    PooledBuf<uint32_t> perm_a, perm_b;
+    PooledBuf<uint64_t> col_a, col_b;
+    PooledBuf<uint8_t> temp;
+    const uint32_t* perm = nullptr;
+    SortedPerm(uint32_t n, size_t temp_bytes) : perm_a(n), perm_b(n), col_a(n), col_b(n), temp(temp_bytes) {}
+};
+std::unique_ptr<SortedPerm> sort_records(const UtxoKeyRec* recs, uint32_t n, bool by_tag, hipStream_t st);
 
 }  // namespace upow

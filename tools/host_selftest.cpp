@@ -291,6 +291,98 @@ static void test_state_digest() {
     for (int x = 0; x < 1024; ++x) CHECK(uint16_t(lane(lo, x) + lane(hi, x)) == lane(one, x));
 }
 
+// UTXO proofs (csrc/utxo_merkle_host.cpp): the known roots of the sets {}, {A}, {A, B, C} of the state digest's entries
+// (computed with hashlib from the recursive RFC 6962 definition), C's payload noise dropped, every leaf of a 300-entry
+// tree rehashed up its audit path, absence at both ends, and the same tree from every thread count.
+static std::vector<uint8_t> fold_path(const MerkleProveOut& p, size_t j, uint64_t count) {
+    uint32_t len;
+    std::memcpy(&len, &p.entry[j * kMerkleSlot + 108], 4);
+    std::vector<uint8_t> m{0x00};
+    m.insert(m.end(), &p.entry[j * kMerkleSlot], &p.entry[j * kMerkleSlot] + len);
+    std::vector<uint8_t> r = sha(m.data(), m.size());
+    uint64_t fn = p.position[j], sn = count - 1;  // RFC 9162 2.1.3.2
+    for (uint32_t k = p.path_first[j]; k < p.path_first[j + 1]; ++k) {
+        const uint8_t* h = &p.path[32 * size_t(k)];
+        std::vector<uint8_t> node{0x01};
+        if ((fn & 1) || fn == sn) {
+            node.insert(node.end(), h, h + 32);
+            node.insert(node.end(), r.begin(), r.end());
+            while (fn && !(fn & 1)) fn >>= 1, sn >>= 1;
+        } else {
+            node.insert(node.end(), r.begin(), r.end());
+            node.insert(node.end(), h, h + 32);
+        }
+        r = sha(node.data(), node.size());
+        fn >>= 1, sn >>= 1;
+    }
+    CHECK(sn == 0);
+    return r;
+}
+
+static void test_merkle_host() {
+    uint8_t ta[32], tb[32], tc[32];
+    std::vector<uint8_t> aa{42}, ab;
+    for (int i = 0; i < 32; ++i) {
+        ta[i] = uint8_t(i);
+        tb[i] = uint8_t(32 + i);
+        tc[i] = 0xff;
+        aa.push_back(uint8_t(1 + i));
+    }
+    for (int i = 0; i < 64; ++i) ab.push_back(uint8_t(100 + i));
+    const struct { int set; const char* root; } known[] = {
+        {0, "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855"},
+        {1, "d68a3c66ecda39a9b29757e377b40021584637bb9d1f9564ca3bd761b0fa8e5a"},
+        {7, "55a26afe2b59d453ddabdd176be6de0df1f39d6a98386e104ea651b2d26daa3b"}};
+    for (const auto& k : known) {
+        std::vector<uint8_t> recs, pay;
+        if (k.set & 4) put_entry(recs, pay, tc, 7, 6, 1, 999, {'x', 'y', 'z'});  // canonicalised: C
+        if (k.set & 2) put_entry(recs, pay, tb, 255, 0, 1, 600000000, ab);
+        if (k.set & 1) put_entry(recs, pay, ta, 0, 0, 0, 1, aa);
+        for (int threads : {1, 3}) {
+            const int64_t id = utxo_merkle_build_records_host(recs.data(), pay.data(), int64_t(recs.size() / 40), threads);
+            const MerkleInfo info = utxo_merkle_info(id);
+            CHECK(std::vector<uint8_t>(info.root, info.root + 32) == unhex(k.root));
+            CHECK(info.count == recs.size() / 40 && !info.on_device);
+            utxo_merkle_free(id);
+        }
+    }
+    std::mt19937 rng(23);
+    std::vector<uint8_t> recs, pay;
+    for (int i = 0; i < 300; ++i) {
+        uint8_t t[32];
+        for (auto& x : t) x = uint8_t(rng());
+        t[0] = uint8_t(1 + i % 200);  // never the smallest or the greatest possible txid
+        std::vector<uint8_t> addr(size_t(i % 3 == 0 ? 33 : (i % 3 == 1 ? 64 : 0)));
+        for (auto& x : addr) x = uint8_t(rng());
+        put_entry(recs, pay, t, rng() & 0xff, rng() % 7, rng() & 1, (uint64_t(rng()) << 20) | rng(), addr);
+    }
+    uint64_t held_n = 0, held_b = 0, n1 = 0, b1 = 0;
+    utxo_merkle_held(&held_n, &held_b);
+    const int64_t one = utxo_merkle_build_records_host(recs.data(), pay.data(), 300, 1);
+    const int64_t many = utxo_merkle_build_records_host(recs.data(), pay.data(), 300, 16);
+    const MerkleInfo info = utxo_merkle_info(one), info16 = utxo_merkle_info(many);
+    CHECK(std::memcmp(info.root, info16.root, 32) == 0 && info.count == 300 && info.levels == 10);
+    std::vector<uint8_t> queries = recs;
+    queries.resize(40 * 302, 0);  // + the smallest outpoint and the greatest
+    std::memset(&queries[40 * 301], 0xff, 33);
+    MerkleProveOut p;
+    utxo_merkle_prove(many, queries.data(), 302, p);
+    CHECK(p.present.size() == 302 && p.first.back() == 302 && p.position.size() == 302);
+    for (size_t j = 0; j < p.position.size(); ++j)
+        CHECK(fold_path(p, j, 300) == std::vector<uint8_t>(info.root, info.root + 32));
+    for (int i = 0; i < 300; ++i) CHECK(p.present[size_t(i)] == 1);
+    CHECK(!p.present[300] && p.position[300] == 0 && !p.present[301] && p.position[301] == 299);
+    utxo_merkle_prove(one, queries.data(), 0, p);
+    CHECK(p.present.empty() && p.first.size() == 1 && p.path.empty());
+    utxo_merkle_free(one);
+    utxo_merkle_held(&n1, &b1);
+    CHECK(n1 == held_n + 1 && b1 == held_b + info16.bytes);
+    utxo_merkle_free(many);
+    utxo_merkle_free(many);  // an unknown id is ignored
+    utxo_merkle_held(&n1, &b1);
+    CHECK(n1 == held_n && b1 == held_b);
+}
+
 static void test_pow_host() {
     PowJobHost job;
     job.header.assign(108, 0);
@@ -310,6 +402,7 @@ int main() {
     test_p256();
     test_vanity_host();
     test_state_digest();
+    test_merkle_host();
     test_pow_host();
     if (failures) {
         std::fprintf(stderr, "%d failure(s)\n", failures);

@@ -4,7 +4,7 @@
 #   tools/sanitize_host.sh [outdir]          (FUZZ_SECONDS=N per fuzz target, default 20)
 #
 # 1. tools/host_selftest.cpp + the host crypto (SHA-256, SHA-NI, base58, P-256, the vanity walk's host path, the state
-#    digest's host routine) under ASan + UBSan;
+#    digest's host routine, the Merkle tree's host twin) under ASan + UBSan;
 #    the host worker pool (csrc/thread_pool.h) under ThreadSanitizer.
 # 2. libFuzzer + ASan + UBSan on the parsers of untrusted network input: the tx decoder every pushed tx and
 #    every peer block goes through (csrc/txdecode.h, tools/fuzz/fuzz_txdecode.cpp) and the HTTP/1.1 +
@@ -40,7 +40,7 @@ stale() {  # $1 = object, rest = inputs: rebuild when any input is newer
   for i in "$@"; do [ "$i" -nt "$o" ] && return 0; done
   return 1
 }
-HDRS="csrc/native.h csrc/sha256_common.h csrc/thread_pool.h csrc/p256_field.h csrc/p256_verify.h csrc/p256_steps.h csrc/p256_probe.h csrc/p256_sign.h csrc/p256_vanity.h"
+HDRS="csrc/native.h csrc/sha256_common.h csrc/thread_pool.h csrc/utxo_merkle.h csrc/p256_field.h csrc/p256_verify.h csrc/p256_steps.h csrc/p256_probe.h csrc/p256_sign.h csrc/p256_vanity.h"
 echo "== [1] host selftest (ASan + UBSan) and host pool (TSan)"
 # the verify TU, the one-lane batch kernel's TU it launches, the fixed-base tables, decompression, the signers, the vanity walk
 for h in p256 p256_batch p256_tables p256_keys p256_sign p256_vanity; do
@@ -49,14 +49,14 @@ for h in p256 p256_batch p256_tables p256_keys p256_sign p256_vanity; do
       -c csrc/$h.hip -o "$OUT/$h.o"
   fi
 done
-for f in csrc/sha256_host.cpp csrc/sha256_ni.cpp csrc/base58.cpp csrc/p256_host.cpp csrc/utxo_digest_host.cpp tools/host_selftest.cpp; do
+for f in csrc/sha256_host.cpp csrc/sha256_ni.cpp csrc/base58.cpp csrc/p256_host.cpp csrc/utxo_digest_host.cpp csrc/utxo_merkle_host.cpp tools/host_selftest.cpp; do
   o="$OUT/$(basename "${f%.cpp}").o"
   if stale "$o" "$f" $HDRS; then
     $CXX $CFLAGS -fsanitize=address,undefined -fno-sanitize-recover=undefined -pthread -c "$f" -o "$o"
   fi
 done
 $CXX -fsanitize=address,undefined -pthread "$OUT"/host_selftest.o "$OUT"/p256.o "$OUT"/p256_batch.o "$OUT"/p256_tables.o "$OUT"/p256_keys.o "$OUT"/p256_sign.o "$OUT"/p256_vanity.o "$OUT"/sha256_host.o \
-  "$OUT"/sha256_ni.o "$OUT"/base58.o "$OUT"/p256_host.o "$OUT"/utxo_digest_host.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o "$OUT/host_selftest"
+  "$OUT"/sha256_ni.o "$OUT"/base58.o "$OUT"/p256_host.o "$OUT"/utxo_digest_host.o "$OUT"/utxo_merkle_host.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -o "$OUT/host_selftest"
 # leak checking off: the HIP runtime keeps process-lifetime allocations
 ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 "$OUT/host_selftest"
 # ThreadSanitizer on the host worker pool (csrc/thread_pool.h)

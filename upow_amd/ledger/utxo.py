@@ -287,6 +287,179 @@ def _masked(recs: np.ndarray, pay: np.ndarray, mask: int):
     return np.ascontiguousarray(recs[keep]), None if pay is None else np.ascontiguousarray(pay[keep])
 
 
+# UTXO proofs (``UtxoIndex.merkle_snapshot``): an RFC 6962 Merkle tree over the entries E above, in ascending order
+# of E's first 34 bytes (txid, index, tag), so that ONE entry can be checked against ``(root, count)`` by somebody who
+# holds nothing else: ``leaf = SHA-256(0x00 | E)``, ``node = SHA-256(0x01 | left | right)``, the tree of n leaves
+# split at the largest power of two below n, the empty set's root SHA-256 of the empty string. The definition is in
+# csrc/native.h and docs/WIRE_FORMAT.md; the verifier is ledger/utxo_proof.py (pure Python).
+def entries_of(recs: np.ndarray, pay: Optional[np.ndarray]) -> List[bytes]:
+    """E of every packed record + payload (``pay=None``: every entry has L = 0), in the order given."""
+    recs, pay = _digest_arrays(recs, pay)
+    raw = recs.tobytes()
+    praw = pay.tobytes() if pay is not None else None
+    out = []
+    for i in range(len(recs)):
+        r = raw[40 * i:40 * i + 40]
+        head, amount, addr = bytes((r[32], r[36], 0, 0)), bytes(8), b''
+        if praw is not None:
+            p = praw[80 * i:80 * i + 80]
+            length = int.from_bytes(p[8:12], 'little')
+            if length in (33, 64):
+                head, amount, addr = bytes((r[32], r[36], p[12] & 1, length)), p[0:8], p[16:16 + length]
+        out.append(r[:32] + head + amount + addr)
+    return out
+
+
+class _ReferenceTree:
+    """The tree of sorted entries from the RFC's recursive definition (MTH and PATH of RFC 9162 2.1.1 / 2.1.3.1),
+    subtree hashes kept by leaf range: what ``merkle_of`` / ``prove_of`` and the ``host-py`` backend run."""
+
+    def __init__(self, entries: List[bytes]):
+        from .utxo_proof import leaf_hash
+        self.entries = sorted(entries, key=lambda e: e[:34])  # stable: equal keys keep their order
+        self.keys = [e[:34] for e in self.entries]
+        self.leaves = [leaf_hash(e) for e in self.entries]
+        self.memo: Dict[Tuple[int, int], bytes] = {}
+
+    def mth(self, lo: int, hi: int) -> bytes:
+        from .utxo_proof import EMPTY_ROOT, node_hash
+        if hi == lo:
+            return EMPTY_ROOT
+        if hi - lo == 1:
+            return self.leaves[lo]
+        got = self.memo.get((lo, hi))
+        if got is None:
+            k = 1 << ((hi - lo - 1).bit_length() - 1)  # the largest power of two below n
+            got = self.memo[(lo, hi)] = node_hash(self.mth(lo, lo + k), self.mth(lo + k, hi))
+        return got
+
+    def path(self, m: int, lo: int, hi: int) -> List[bytes]:
+        if hi - lo == 1:
+            return []
+        k = 1 << ((hi - lo - 1).bit_length() - 1)
+        if m < lo + k:
+            return self.path(m, lo, lo + k) + [self.mth(lo + k, hi)]
+        return self.path(m, lo + k, hi) + [self.mth(lo, lo + k)]
+
+    def levels(self) -> int:
+        n = len(self.entries)
+        return 0 if n == 0 else 1 + (n - 1).bit_length()
+
+    def prove(self, outpoints):
+        import bisect
+        from .utxo_proof import LeafProof, OutpointProof, query_key
+        n, out = len(self.entries), []
+        for tx_hash, index in outpoints:
+            want = query_key(tx_hash, index)
+            at = bisect.bisect_left(self.keys, want + b'\0')
+            end = at
+            while end < n and self.keys[end][:33] == want:
+                end += 1
+            pos = list(range(at, end)) if end > at else [p for p in (at - 1, at) if 0 <= p < n]
+            out.append(OutpointProof(tx_hash, index, end > at,
+                                     [LeafProof(p, self.entries[p], self.path(p, 0, n)) for p in pos]))
+        return out
+
+
+def merkle_of(recs: np.ndarray, pay: Optional[np.ndarray]) -> Tuple[bytes, int]:
+    """``(root, count)`` of packed records + payloads with hashlib, from the recursive RFC definition: the reference
+    the native and the HBM builds are tested against."""
+    t = _ReferenceTree(entries_of(recs, pay))
+    return t.mth(0, len(t.entries)), len(t.entries)
+
+
+def prove_of(recs: np.ndarray, pay: Optional[np.ndarray], outpoints: Sequence[Outpoint]):
+    """The :class:`~upow_amd.ledger.utxo_proof.OutpointProof` of each ``(tx_hash, index)`` in the set of packed
+    records + payloads: the reference, as :func:`merkle_of`."""
+    return _ReferenceTree(entries_of(recs, pay)).prove(outpoints)
+
+
+class MerkleSnapshot:
+    """The Merkle tree of one state of an index (or of a record set): ``root``, ``count``, ``levels`` (stored levels,
+    the leaves' included) and ``nbytes`` held, and :meth:`prove`. It owns its buffers (HBM for the GPU backend) and
+    answers whatever happens to the index afterwards, until :meth:`close`; also a context manager."""
+
+    def __init__(self, lib=None, sid: Optional[int] = None, tree: Optional[_ReferenceTree] = None):
+        self._lib, self._sid, self._tree = lib, sid, tree
+        if tree is not None:
+            self.root, self.count, self.levels = tree.mth(0, len(tree.entries)), len(tree.entries), tree.levels()
+            self.nbytes = sum(map(len, tree.entries)) + 32 * (2 * self.count)
+            self.on_device = False
+        else:
+            info = lib.utxo_merkle_info(sid)
+            self.root, self.count, self.levels = info['root'], int(info['count']), int(info['levels'])
+            self.nbytes, self.on_device = int(info['bytes']), bool(info['on_device'])
+
+    def prove(self, outpoints: Sequence[Outpoint]):
+        """One :class:`~upow_amd.ledger.utxo_proof.OutpointProof` per ``(tx_hash, index)``, in the order asked."""
+        from .utxo_proof import LeafProof, OutpointProof
+        outpoints = [(str(h), int(i)) for h, i in outpoints]
+        if self._tree is not None:
+            return self._tree.prove(outpoints)
+        if self._sid is None:
+            raise ValueError('the snapshot is closed')
+        if not outpoints:
+            return []
+        for _, i in outpoints:
+            if not 0 <= i <= 255:
+                raise ValueError('an output index is in 0..255')
+        present, first, position, slots, path_first, path = self._lib.utxo_merkle_prove(self._sid, pack_records(outpoints))
+        leaves = []
+        for j, pos in enumerate(position):
+            slot = slots[112 * j:112 * j + 112]
+            hashes = path[32 * path_first[j]:32 * path_first[j + 1]]
+            leaves.append(LeafProof(int(pos), slot[:int.from_bytes(slot[108:112], 'little')],
+                                    [hashes[k:k + 32] for k in range(0, len(hashes), 32)]))
+        return [OutpointProof(h, i, bool(present[k]), leaves[first[k]:first[k + 1]])
+                for k, (h, i) in enumerate(outpoints)]
+
+    def close(self):
+        sid, self._sid, self._tree = self._sid, None, None
+        if sid is not None and self._lib is not None:
+            self._lib.utxo_merkle_free(sid)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __repr__(self):
+        return f'MerkleSnapshot({self.root.hex()}, count={self.count})'
+
+
+def records_merkle(recs: np.ndarray, pay: Optional[np.ndarray], device: Optional[str] = None,
+                   threads: Optional[int] = None, *, launch_lever: int = 0) -> MerkleSnapshot:
+    """The :class:`MerkleSnapshot` of packed records + payloads (``pay=None``: no payloads). ``device='gpu'``: the
+    kernels of csrc/utxo_merkle.hip; ``'cpu'``: the native host routine (csrc/utxo_merkle_host.cpp) on ``threads``
+    (default 16) host threads, or the hashlib reference when the extension is not built. ``None``: the GPU when
+    there is one."""
+    recs, pay = _digest_arrays(recs, pay)
+    if device is None:
+        from ..ops.native import gpu_available
+        device = 'gpu' if gpu_available() else 'cpu'
+    if device not in ('gpu', 'cpu'):
+        raise ValueError("device is 'gpu', 'cpu' or None")
+    praw = None if pay is None else pay.view(np.uint8)
+    if device == 'gpu':
+        from ..ops.native import require_gpu
+        L = require_gpu()
+        return MerkleSnapshot(L, L.utxo_merkle_build_records(recs, praw, launch_lever))
+    try:
+        from ..ops.native import lib
+        L = lib()
+        fn = L.utxo_merkle_build_records_host
+    except (ImportError, AttributeError):
+        return MerkleSnapshot(tree=_ReferenceTree(entries_of(recs, pay)))
+    return MerkleSnapshot(L, fn(recs, praw, DIGEST_HOST_THREADS if threads is None else int(threads)))
+
+
 # UTXO diff (``UtxoIndex.diff_records``): WHERE the index and a record set differ, an entry being what the state
 # digest hashes (E above) and the outpoint (txid, index) alone its identity. Of the index I against the other set O:
 # ``missing`` are the outpoints of O that I lacks, ``extra`` those of I that O lacks, ``changed`` those in both whose
@@ -573,6 +746,10 @@ class _HostBackend:
         """The state digest of the entries with a tag in ``tag_mask``: the reference (``state_digest_of``)."""
         return state_digest_of(*_masked(*self.records_payload(), tag_mask))
 
+    def merkle_snapshot(self, tag_mask, launch_lever=0):
+        """The Merkle tree of the entries with a tag in ``tag_mask``: the reference (``_ReferenceTree``)."""
+        return MerkleSnapshot(tree=_ReferenceTree(entries_of(*_masked(*self.records_payload(), tag_mask))))
+
     def diff(self, recs, pay, tag_mask, limit, chunk_records=0):
         """The index against the record set: the reference (``diff_of``) on a dump."""
         return diff_of(recs, pay, *self.records_payload(), tag_mask=tag_mask, limit=limit)
@@ -657,6 +834,13 @@ class _NativeHostBackend:
         (``utxo_records_digest_host``) on the host pool."""
         recs, pay = _masked(*self.records_payload(), tag_mask)
         return StateDigest(*self.L.utxo_records_digest_host(recs, pay.view(np.uint8), DIGEST_HOST_THREADS))
+
+    def merkle_snapshot(self, tag_mask, launch_lever=0):
+        """The Merkle tree of the entries with a tag in ``tag_mask``: a dump, then the native host routine
+        (``utxo_merkle_build_records_host``) on the host pool."""
+        recs, pay = _masked(*self.records_payload(), tag_mask)
+        return MerkleSnapshot(self.L, self.L.utxo_merkle_build_records_host(recs, pay.view(np.uint8),
+                                                                              DIGEST_HOST_THREADS))
 
     def diff(self, recs, pay, tag_mask, limit, chunk_records=0):
         """The index against the record set: a dump, then the join in numpy (``diff_vectorised``)."""
@@ -827,6 +1011,12 @@ class _GpuBackend:
         (``utxo_state_digest``: live slots queued per wave, 1 + 64 SHA-256 compressions per entry, the lanes
         summed across each wave in registers); 8 stripes of lane sums (33 KB) come back. ``grid_blocks``: test lever."""
         return StateDigest(*self.L.utxo_state_digest(self.h, tag_mask, grid_blocks))
+
+    def merkle_snapshot(self, tag_mask, launch_lever=0):
+        """The Merkle tree of the live entries with a tag in ``tag_mask``, built in HBM (``utxo_merkle_build``: one
+        collection of the table under one hold of its lock, K12's radix sort with the tag as one more column, one
+        lane per leaf, one launch per level); 32 bytes come back. ``launch_lever``: test lever."""
+        return MerkleSnapshot(self.L, self.L.utxo_merkle_build(self.h, tag_mask, launch_lever))
 
     def diff(self, recs, pay, tag_mask, limit, chunk_records=0):
         """The index against the record set (tags in ``tag_mask`` only) from ONE pass over the HBM table
@@ -1114,6 +1304,16 @@ class UtxoIndex:
         behind any queued block apply (``grid_blocks`` sizes its launch: a test lever); host backends: a dump
         and 65 compressions per entry on the CPU."""
         return self.be.state_digest(_tag_mask(tags), grid_blocks)
+
+    @_locked
+    def merkle_snapshot(self, tags: Optional[Iterable[int]] = None, *, launch_lever: int = 0) -> MerkleSnapshot:
+        """A :class:`MerkleSnapshot` of every live entry of the tables ``tags`` (default: all seven): the RFC 6962
+        tree over the entries in (txid, index, tag) order, whose ``(root, count)`` commits to the set and whose
+        :meth:`MerkleSnapshot.prove` shows for any outpoint that it is live with this amount and owner, or that it
+        is not (verified by ledger/utxo_proof.py). The snapshot owns its memory, about 176 bytes per entry (HBM on the
+        GPU backend, built there by csrc/utxo_merkle.hip), and keeps answering for this state after the index moves
+        on. ``launch_lever`` is a test lever."""
+        return self.be.merkle_snapshot(_tag_mask(tags), launch_lever)
 
     @_locked
     def diff_records(self, recs: np.ndarray, pay: Optional[np.ndarray] = None, tags: Optional[Iterable[int]] = None,

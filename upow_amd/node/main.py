@@ -208,6 +208,7 @@ async def startup():
     access = AccessControl()
     path = os.environ.get('UPOW_DATABASE_PATH') or config.data_path('ledger.sqlite3')
     db = await Database.create(path=path)
+    utxo_proofs.reset()  # a snapshot belongs to the ledger it was built from
     # block validation/apply and every cluster collective run on the ledger thread
     ledger_worker.start()
     from ..ledger import lean
@@ -963,6 +964,108 @@ async def get_addresses_info(request: Request,
     outputs = await db.get_spendable_outputs_many(addresses, check_pending_txs)
     return {'ok': True, 'result': [{'address': a, 'balance': '{:f}'.format(sum(o.amount for o in outputs[a])),
                                     'spendable_outputs': _outs(outputs[a])} for a in addresses]}
+
+
+class UtxoProofs:
+    """The node's Merkle snapshot of the UTXO index (``UtxoIndex.merkle_snapshot`` over all seven tables): at most
+    one, for the current tip. The first request after the tip moved drops the old one and builds the new one;
+    requests that arrive meanwhile wait for that one build. Nothing of it runs on the event loop: the old snapshot
+    is let go of on an executor thread (freeing 0.9 GB of HBM synchronises the device), and so are the build and the
+    dump. The ledger lock, under which the tip and the index belong together, is held for the GPU backend's build
+    (milliseconds) and on a host backend for the dump of the index only: the tree, seconds of hashing and sorting
+    at 5 M entries there, is built from that copy after the lock is released. About 176 bytes per entry, in HBM on a
+    GPU node."""
+
+    def __init__(self):
+        self.state = None  # {'snapshot', 'root', 'count', 'block_hash', 'height'}
+        self.task = None
+        self.builds = 0
+
+    async def _build(self):
+        from ..ledger.utxo import ALL_TAGS_MASK, _masked, records_merkle
+        loop = asyncio.get_running_loop()
+        on_gpu = db.utxo.backend_name == 'gpu'
+
+        async def under_lock():
+            tip = await db.get_last_block()
+            inner = asyncio.get_running_loop()
+            if on_gpu:
+                return tip, await inner.run_in_executor(None, db.utxo.merkle_snapshot)
+            return tip, await inner.run_in_executor(None, lambda: db.utxo.records_payload(sort=False))
+        old, self.state = self.state, None
+        self.builds += 1
+        if old is not None:
+            old['retired'] = True
+            await self._close_if_unused(old)
+        tip, got = await on_ledger(_locked, under_lock)
+        snap = got if on_gpu else await loop.run_in_executor(
+            None, lambda: records_merkle(*_masked(*got, ALL_TAGS_MASK), device='cpu'))
+        self.state = {'snapshot': snap, 'root': snap.root.hex(), 'count': snap.count, 'users': 0, 'retired': False,
+                      'block_hash': tip['hash'] if tip else None, 'height': int(tip['id']) if tip else 0}
+        return self.state
+
+    @staticmethod
+    async def _close_if_unused(state: dict):
+        """Free a retired snapshot once no request proves from it, on an executor thread."""
+        if state['retired'] and state['users'] == 0 and state['snapshot'] is not None:
+            snap, state['snapshot'] = state['snapshot'], None
+            await asyncio.get_running_loop().run_in_executor(None, snap.close)
+
+    async def prove(self, outpoints) -> tuple:
+        """(the state the proofs hold against, the proofs), proved on an executor thread; the snapshot stays alive
+        for the call even when the tip moves meanwhile."""
+        state = await self.current()
+        while state['snapshot'] is None:  # retired and freed between its build and this request's turn
+            state = await self.current()
+        state['users'] += 1
+        try:
+            proofs = await asyncio.get_running_loop().run_in_executor(None, state['snapshot'].prove, outpoints)
+        finally:
+            state['users'] -= 1
+            await self._close_if_unused(state)
+        return state, proofs
+
+    async def current(self) -> dict:
+        tip = await db.get_last_block()
+        state = self.state
+        if state is not None and state['block_hash'] == (tip['hash'] if tip else None):
+            return state
+        if self.task is None or self.task.done():
+            self.task = asyncio.ensure_future(self._build())
+        return await asyncio.shield(self.task)
+
+    def reset(self):
+        self.state = self.task = None
+
+
+utxo_proofs = UtxoProofs()
+
+
+def _commitment(state: dict) -> dict:
+    return {k: state[k] for k in ('root', 'count', 'block_hash', 'height')}
+
+
+@app.get('/get_utxo_root')
+@limiter.limit('15/second')
+async def get_utxo_root(request: Request):
+    """The Merkle commitment of the UTXO index at the tip (the project's own route): ``{root, count, block_hash,
+    height}``. Compare it between nodes; with it, ``/get_utxo_proofs`` answers can be checked by a client that
+    holds nothing else (ledger/utxo_proof.py)."""
+    return {'ok': True, 'result': _commitment(await utxo_proofs.current())}
+
+
+@app.post('/get_utxo_proofs')
+@limiter.limit('15/second')
+async def get_utxo_proofs(request: Request,
+                          outpoints: Annotated[list[tuple[str, int]], Body(min_length=1, max_length=1000, embed=True)]):
+    """For 1 to 1000 outpoints ``[[tx_hash, index], ...]``, in request order: the proof that the outpoint is live
+    with this amount and owner, or that it is not, against the ``root``/``count`` the answer carries (with the
+    ``block_hash`` and ``height`` they belong to). The project's own route."""
+    for tx_hash, index in outpoints:
+        if not re.fullmatch(r'[0-9a-fA-F]{64}', tx_hash) or not 0 <= index <= 255:
+            return JSONResponse(status_code=422, content={'ok': False, 'error': 'an outpoint is [64 hex digits, 0..255]'})
+    state, proofs = await utxo_proofs.prove([(h.lower(), i) for h, i in outpoints])
+    return {'ok': True, 'result': {**_commitment(state), 'proofs': [p.to_json() for p in proofs]}}
 
 
 @app.get('/get_address_transactions')

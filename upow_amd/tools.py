@@ -33,6 +33,15 @@ and not in the index, ``extra`` the reverse, and a changed entry shows both side
 most ``--limit`` (default 65536) lines per kind. The last line printed is the summary ``{"equal", "missing", "extra",
 "changed", "compared", "entries", "truncated", "backend", "seconds"}`` with the exact counts. Exit status 1 unless
 the sets are equal.
+``python -m upow_amd.tools utxo-root [--db PATH] [--snapshot F]``: the Merkle commitment of the UTXO index over all
+seven tables (``UtxoIndex.merkle_snapshot``; on a GPU node built in HBM, csrc/utxo_merkle.hip), or with
+``--snapshot F`` of that file's records: one JSON line ``{"root", "count", "levels", "backend", "seconds"}``.
+``python -m upow_amd.tools utxo-proof TXHASH:INDEX [...] [--db PATH] [--snapshot F] [--out F]``: for each outpoint
+the proof that it is in that set with its amount and owner, or that it is not, as one JSON document ``{"root",
+"count", "backend", "proofs"}`` (to ``--out F`` when given). ``utxo-proof --check FILE [--root HEX --count N]``
+verifies such a document offline with ledger/utxo_proof.py alone, against the commitment given (without one, against
+the document's own, which shows that it is consistent and no more): one line per outpoint, then the summary; exit
+status 1 when a proof fails.
 ``python -m upow_amd.tools materialise --db <rankN ledger>``: bring a lean cluster follower's SQL tables to its
 tip from its op log (ledger/lean.py); every other command does this first when the ledger has an op log.
 ``python -m upow_amd.tools sign-batch --keys F --digests F --out F [--device gpu|cpu]``: bulk RFC 6979 signing
@@ -147,6 +156,60 @@ async def utxo_digest(path: str = None, snapshot_path: str = None, full: bool = 
     return res
 
 
+async def _merkle_snapshot(path: str = None, snapshot_path: str = None, db: Database = None):
+    """(Merkle snapshot, backend name) of the index over all seven tables, or of a snapshot file's records and
+    payloads (built on the GPU when there is one)."""
+    from .ledger.utxo import ALL_TAGS_MASK, _masked, records_merkle
+    if snapshot_path:
+        from .ledger import snapshot
+        _, recs, pay = snapshot.read(snapshot_path)
+        snap = records_merkle(*_masked(recs, pay, ALL_TAGS_MASK))
+        return snap, 'gpu' if snap.on_device else 'host'
+    db = db or await open_ledger(path)
+    return db.utxo.merkle_snapshot(), db.utxo.backend_name
+
+
+async def utxo_root(path: str = None, snapshot_path: str = None, db: Database = None) -> dict:
+    """The ``utxo-root`` command's line: the Merkle commitment ``(root, count)`` of the index, or of a snapshot
+    file."""
+    import time
+    t = time.perf_counter()
+    snap, backend = await _merkle_snapshot(path, snapshot_path, db)
+    with snap:
+        return {'root': snap.root.hex(), 'count': snap.count, 'levels': snap.levels, 'backend': backend,
+                'seconds': round(time.perf_counter() - t, 6)}
+
+
+async def utxo_proofs(outpoints, path: str = None, snapshot_path: str = None, db: Database = None) -> dict:
+    """The ``utxo-proof`` command's document: the commitment and one proof per outpoint, in the order asked."""
+    snap, backend = await _merkle_snapshot(path, snapshot_path, db)
+    with snap:
+        return {'root': snap.root.hex(), 'count': snap.count, 'backend': backend,
+                'proofs': [p.to_json() for p in snap.prove(outpoints)]}
+
+
+def check_proofs(doc: dict, root_hex: str = None, count: int = None):
+    """``utxo-proof --check``: verify a ``utxo-proof`` document offline with ledger/utxo_proof.py alone, against
+    the commitment given (else the document's own, which shows consistency only). One line per outpoint and the
+    summary ``{"ok", "root", "count", "present", "absent", "failed"}``."""
+    from .ledger import utxo_proof
+    root = bytes.fromhex(root_hex if root_hex is not None else doc['root'])
+    count = int(doc['count'] if count is None else count)
+    lines, tally = [], {'present': 0, 'absent': 0, 'failed': 0}
+    for p in doc['proofs']:
+        line = {'tx_hash': p.get('tx_hash'), 'index': p.get('index')}
+        try:
+            found = utxo_proof.verify_outpoint_all(root, count, p['tx_hash'], p['index'], p)
+            line.update(result='present' if found else 'absent', entries=found)
+            for e in found:
+                e['amount'] = str(Decimal(e['amount']) / SMALLEST)
+        except (utxo_proof.ProofError, KeyError, TypeError, ValueError) as e:
+            line.update(result='failed', error=str(e))
+        tally[line['result']] += 1
+        lines.append(line)
+    return lines, {'ok': tally['failed'] == 0, 'root': root.hex(), 'count': count, **tally}
+
+
 def _diff_entry(rec, pay) -> dict:
     """One side of a diff line: the fields of an entry that the diff compares (no payload: nulls)."""
     from .ledger.utxo import TABLE_BY_TAG
@@ -251,7 +314,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('command', choices=['rebuild-utxo', 'utxo-hash', 'snapshot', 'verify-utxo', 'address-utxos',
                                         'holders', 'materialise', 'sign-batch', 'vanity', 'utxo-digest',
-                                        'utxo-diff'])
+                                        'utxo-diff', 'utxo-root', 'utxo-proof'])
     ap.add_argument('address', nargs='*')
     ap.add_argument('--db', default=None)
     ap.add_argument('--out', default=None)
@@ -261,7 +324,9 @@ def main(argv=None):
     ap.add_argument('--top', type=int, default=None)
     ap.add_argument('--by', default='spendable,stake')
     ap.add_argument('--ignore-case', action='store_true')
-    ap.add_argument('--count', type=int, default=1)
+    ap.add_argument('--count', type=int, default=None)  # vanity: keys to find (1); utxo-proof --check: leaves
+    ap.add_argument('--check', default=None)
+    ap.add_argument('--root', default=None)
     ap.add_argument('--max-keys', type=int, default=None)
     ap.add_argument('--snapshot', default=None)
     ap.add_argument('--full', action='store_true')
@@ -276,6 +341,7 @@ def main(argv=None):
         print(json.dumps(res))
         return 1 if res['failed'] else 0
     elif a.command == 'vanity':
+        a.count = 1 if a.count is None else a.count
         if len(a.address) != 1 or a.count < 1:
             ap.error('vanity needs one PREFIX and --count >= 1')
         from .wallet import vanity
@@ -319,6 +385,43 @@ def main(argv=None):
             raise SystemExit(f'utxo-digest: {e}')
         print(json.dumps(res))
         return 0 if res.get('match', True) else 1
+    elif a.command == 'utxo-root':
+        try:
+            print(json.dumps(asyncio.run(utxo_root(a.db, a.snapshot))))
+        except (ValueError, OSError) as e:
+            raise SystemExit(f'utxo-root: {e}')
+        return 0
+    elif a.command == 'utxo-proof':
+        if a.check:
+            if a.address or (a.root is None) != (a.count is None):
+                ap.error('utxo-proof --check FILE takes no outpoints, and --root HEX and --count N go together')
+            try:
+                with open(a.check) as f:
+                    lines, summary = check_proofs(json.load(f), a.root, a.count)
+            except (ValueError, OSError, KeyError, TypeError) as e:
+                raise SystemExit(f'utxo-proof: {e}')
+            for line in lines:  # one JSON line per outpoint
+                print(json.dumps(line))
+            print(json.dumps(summary))
+            return 0 if summary['ok'] else 1
+        from .ledger.utxo_proof import split_outpoint
+        try:
+            outpoints = [split_outpoint(x) for x in a.address]
+        except ValueError:
+            outpoints = []
+        if not outpoints:
+            ap.error('utxo-proof needs TXHASH:INDEX outpoints (or --check FILE)')
+        try:
+            doc = asyncio.run(utxo_proofs(outpoints, a.db, a.snapshot))
+        except (ValueError, OSError) as e:
+            raise SystemExit(f'utxo-proof: {e}')
+        if a.out:
+            with open(a.out, 'w') as f:
+                json.dump(doc, f)
+            print(json.dumps({'root': doc['root'], 'count': doc['count'], 'proofs': len(doc['proofs']), 'out': a.out}))
+        else:
+            print(json.dumps(doc))
+        return 0
     elif a.command == 'utxo-diff':
         if bool(a.snapshot) == a.sql or (a.against and not a.snapshot):
             ap.error('utxo-diff needs --snapshot FILE (with --against FILE for two files) or --sql')

@@ -1,6 +1,7 @@
 """HTTP-only wallet (reference: upow/upow_wallet/nodeless_wallet.py:31-200).
 
 ``python -m upow_amd.wallet.nodeless {createwallet,send,balance} [-to R] [-d AMOUNT] [-m MSG]``.
+``balance --verify [--peer URL ...]`` does not take the node's word for it: see :func:`verified_balance`.
 Keys in ``<data dir>/upow_wallet.json`` ({"private_keys": [...]}). Coin selection follows the reference
 (single covering input, else smallest-first up to 255 inputs). Unlike the reference, outputs listed
 in ``pending_spent_outputs`` (dicts) are really skipped — the reference compared ``tuple(dict)``
@@ -42,6 +43,72 @@ def get_address_info(address: str):
         i.public_key = string_to_point(address)
         inputs.append(i)
     return Decimal(result['balance']), inputs
+
+
+class VerifyError(Exception):
+    """``balance --verify``: the node's answer does not check."""
+
+
+VERIFY_HELP = ('check every spendable output the node lists against the Merkle root of its UTXO set '
+               '(GET /get_utxo_root, POST /get_utxo_proofs), and that root against each --peer: the node can then '
+               'neither over-report an amount nor show a spent output as unspent. It can still leave outputs out: '
+               'the tree is ordered by outpoint, not by owner, so the proven balance is a lower bound.')
+
+
+def utxo_commitment(url: str) -> dict:
+    """``{root, count, block_hash, height}`` as the node at ``url`` reports it."""
+    r = httpx.get(f"{url.rstrip('/')}/get_utxo_root", timeout=10)
+    res = r.json()['result']
+    return {'root': str(res['root']), 'count': int(res['count']), 'block_hash': res['block_hash'],
+            'height': int(res['height'])}
+
+
+def verified_balance(address: str, peers=()):
+    """The balance of ``address`` that the node can PROVE, and the commitment it was proven against.
+
+    The node's root is compared with each peer's: two different answers for the same ``block_hash`` refuse the
+    whole run (a peer at another block says nothing and is only counted). Then the node must prove every spendable
+    output it listed: present in the tree, in ``unspent_outputs``, not staked, owned by this key, with the amount
+    it claimed (ledger/utxo_proof.py, from the entry bytes alone). What this shows: no listed output is spent,
+    inflated or somebody else's. What it does not show: that the list is complete. The tree is ordered by
+    outpoint, not by owner, so a node can still leave outputs out."""
+    from ..constants import SMALLEST
+    from ..ledger import utxo_proof
+    from ..utils.codec import address_forms
+    own = utxo_commitment(node_url())
+    agreeing = 0
+    for peer in peers:
+        theirs = utxo_commitment(peer)
+        if theirs['block_hash'] != own['block_hash']:
+            continue
+        if (theirs['root'], theirs['count']) != (own['root'], own['count']):
+            raise VerifyError(f"{peer} reports another UTXO root for block {own['block_hash']}: "
+                              f"{theirs['root']} ({theirs['count']}) against {own['root']} ({own['count']})")
+        agreeing += 1
+    _, inputs = get_address_info(address)
+    forms = {str(f) for f in address_forms(address)}
+    proven = Decimal(0)
+    for at in range(0, len(inputs), 1000):
+        chunk = inputs[at:at + 1000]
+        r = httpx.post(f'{node_url()}get_utxo_proofs', json={'outpoints': [[i.tx_hash, i.index] for i in chunk]},
+                       timeout=30)
+        res = r.json()['result']
+        if (res['root'], int(res['count']), res['block_hash']) != (own['root'], own['count'], own['block_hash']):
+            raise VerifyError('the tip moved between the root and the proofs: run again')
+        if len(res['proofs']) != len(chunk):
+            raise VerifyError('the node did not answer every outpoint')
+        for i, proof in zip(chunk, res['proofs']):
+            try:
+                entry = utxo_proof.verify_outpoint(bytes.fromhex(own['root']), own['count'], i.tx_hash, i.index, proof)
+            except utxo_proof.ProofError as e:
+                raise VerifyError(f'{i.tx_hash}:{i.index}: {e}') from None
+            if entry is None:
+                raise VerifyError(f'{i.tx_hash}:{i.index} is listed as spendable but proven absent')
+            if entry['table'] != 'unspent_outputs' or entry['is_stake'] or entry['address'] not in forms or \
+                    Decimal(entry['amount']) / SMALLEST != i.amount:
+                raise VerifyError(f'{i.tx_hash}:{i.index} is not the output the node listed: {entry}')
+            proven += i.amount
+    return proven, {**own, 'peers_agreeing': agreeing, 'outputs': len(inputs)}
 
 
 def create_transaction(private_keys, receiving_address, amount, message: bytes = None, send_back_address=None,
@@ -92,6 +159,9 @@ def main(argv=None):
     ap.add_argument('-to', dest='recipient', required=False)
     ap.add_argument('-d', dest='amount', required=False)
     ap.add_argument('-m', dest='message', required=False)
+    ap.add_argument('--verify', action='store_true', help='balance: ' + VERIFY_HELP)
+    ap.add_argument('--peer', action='append', default=[], metavar='URL',
+                    help='balance --verify: another node whose UTXO root must agree for the same block (repeatable)')
     args = ap.parse_args(argv)
     store = JsonStore(os.environ.get('UPOW_NODELESS_KEY_FILE') or config.data_path('upow_wallet.json'))
     keys = [int(k) for k in store.get('private_keys') or []]
@@ -103,10 +173,21 @@ def main(argv=None):
         total = 0
         for d in keys:
             address = point_to_string(op.public_key(d))
-            bal, _ = get_address_info(address)
+            if args.verify:
+                try:
+                    bal, against = verified_balance(address, args.peer)
+                except VerifyError as e:
+                    print(f'\nAddress: {address}\nREFUSED: {e}')
+                    return 1
+                print(f'\nAddress: {address}\nProven balance: {bal} ({against["outputs"]} outputs proven against UTXO '
+                      f'root {against["root"]}, {against["count"]} entries, block {against["height"]} '
+                      f'{against["block_hash"]}; {against["peers_agreeing"]} of {len(args.peer)} peers at that block '
+                      f'agree; outputs the node left out cannot show)')
+            else:
+                bal, _ = get_address_info(address)
+                print(f'\nAddress: {address}\nPrivate key: {hex(d)}\nBalance: {bal}')
             total += bal
-            print(f'\nAddress: {address}\nPrivate key: {hex(d)}\nBalance: {bal}')
-        print(f'\nTotal Balance: {total}')
+        print(f'\nTotal {"proven balance" if args.verify else "Balance"}: {total}')
     else:
         if not args.recipient or not args.amount:
             ap.error('send needs -to and -d')
