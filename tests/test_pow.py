@@ -84,13 +84,19 @@ def test_gpu_search_ragged_and_variant(gpu):
 
 @pytest.mark.gpu
 def test_gpu_full_sweep_d63(gpu):
-    """One full 2^32 sweep at the bench difficulty: every reported header passes the node check."""
+    """One full 2^32 sweep at the bench difficulty: every reported header passes the node check, and the split
+    kernels (variants 10 and 11, one p = 26 piece) report the nonces of variant 9, which has no lane split."""
     prev, job = _job('6.3', False, seed=5)
     r = search(job, 0, 1 << 32, device='gpu')
     assert r.searched == 1 << 32
     assert 100 < len(r.nonces) < 320  # expectation 2^32 / 22.37M = 192
-    for n in r.nonces[:20]:
+    for n in r.nonces:
         assert check_pow(job.header_with_nonce(n), prev, '6.3')
+    assert len(set(r.nonces)) == len(r.nonces)
+    for variant in (9, 10, 11):
+        v = search(job, 0, 1 << 32, device='gpu', variant=variant)
+        assert v.searched == 1 << 32 and v.candidates == len(v.nonces), variant
+        assert sorted(v.nonces) == sorted(r.nonces), variant
 
 
 def test_miner_tip_watcher_stops_stale_jobs():
