@@ -196,17 +196,18 @@ PYBIND11_MODULE(_native, m) {
     });
 
     m.def("pow_search_gpu", [](py::bytes header, uint32_t tmask, uint32_t tword, uint32_t fs, uint32_t fl,
-                               uint64_t start, uint64_t count, int grid_blocks, uint32_t chunk_iters, uint32_t cap, int variant) {
+                               uint64_t start, uint64_t count, int grid_blocks, uint32_t chunk_iters, uint32_t cap, int variant,
+                               uint32_t claim) {
         PowJobHost j = make_job(header, tmask, tword, fs, fl);
         PowResult r;
         {
             py::gil_scoped_release rel;
-            r = pow_search_gpu(j, start, count, grid_blocks, chunk_iters, cap, variant);
+            r = pow_search_gpu(j, start, count, grid_blocks, chunk_iters, cap, variant, claim);
         }
         return pow_result_tuple(r);
     }, py::arg("header"), py::arg("tmask"), py::arg("tword"), py::arg("frac_shift"), py::arg("frac_limit"),
        py::arg("start"), py::arg("count"), py::arg("grid_blocks") = 0, py::arg("chunk_iters") = 0,
-       py::arg("cap") = 1 << 16, py::arg("variant") = 0);
+       py::arg("cap") = 1 << 16, py::arg("variant") = 0, py::arg("claim") = 0);
 
     m.def("set_node_device", [](int dev) { set_node_device_native(dev); }, py::arg("device"),
           "pin node-side GPU work (verify, decompress, batched SHA-256) to this device from every thread");

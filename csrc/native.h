@@ -52,7 +52,7 @@ std::vector<uint32_t> pow_split_wave_host(const PowJobHost& job, uint32_t vb, ui
 bool pow_check_word_host(const PowJobHost& job, uint32_t v);
 PowResult pow_search_host(const PowJobHost& job, uint64_t start, uint64_t count, int threads);
 PowResult pow_search_gpu(const PowJobHost& job, uint64_t start, uint64_t count, int grid_blocks,
-                         uint32_t chunk_iters, uint32_t cap, int variant);
+                         uint32_t chunk_iters, uint32_t cap, int variant, uint32_t claim = 0);
 
 // ---------------------------------------------------------------- batched SHA-256 (K3/K4/K12)
 // messages packed back to back in `data`, message i = data[offsets[i] .. offsets[i+1])

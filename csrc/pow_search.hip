@@ -34,15 +34,21 @@
 //    front of every v_alignbit_b32 and v_add3_u32 and none doubled up: each K[i] is loaded in a scalar slot of its own,
 //    rounds 12 and 13 are pinned too, and the nonce word, W17 and the range check's add are not VALU instructions any
 //    more: 1,082 VALU instructions per nonce (docs/PERF.md, "PoW scalar slots");
+//  * the default kernel (pow_search_claim_kernel, variant 12) runs variant 11's loop with no fixed share per wave: a
+//    wave claims 32 values of U at a time from a counter until the dispatch's range is used up, and a sweep is one
+//    dispatch. With fixed shares the eight waves of a SIMD finish one after the other, oldest first, and the median
+//    wave lives for 0.54 of its dispatch (docs/PERF.md, "PoW claimed chunks");
 //  * the predicate only needs digest word H0 for difficulty < 8 (8 hex nibbles) -> one compare per
 //    nonce (variant 10: one add and one unsigned compare, (H0 - tword) < width); hits are appended with an atomic to a small candidate list and re-checked exactly on the
 //    host (covers d >= 8 and the d < 1 "whole hash" quirk).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 
 #include "native.h"
@@ -1106,6 +1112,100 @@ __global__ __launch_bounds__(256, 7) void pow_search_fill_kernel(PowJobDev job, 
     }
 }
 
+// Variant 12: variant 11's loop under a claiming wave loop. A dispatch covers the same [u_begin, u_end) as variant
+// 11's, but no wave has a fixed share of it: a wave takes `claim` values of U from *counter (zero when the dispatch
+// starts), runs them and takes the next, until the range is used up, so the eight waves of a SIMD stay live until the
+// pool is empty and not until the oldest of them has done its share (docs/PERF.md, "PoW claimed chunks"). Waves of
+// a block claim independently: no LDS, no barrier. The host keeps (waves + 1) * claim + (u_end - u_begin) below
+// 2^32, so the counter does not wrap before every wave has seen it past the range. `iters` is the share a wave
+// would have had: the host sizes the grid by it; the kernel does not read it.
+// The arguments that only the claim reads (u_begin, u_end, claim, counter) are loaded from the kernel argument
+// segment at each claim, through a pointer that an asm statement redefines so that the loads stay where they are
+// written: held in SGPRs across the hot loop they do not fit next to the 90 it takes, and the compiler spills them
+// to VGPR lanes. PowClaimKernArgs is the kernel's argument list as a struct, which has the segment's layout.
+struct PowClaimKernArgs {
+    PowJobDev job;
+    uint32_t vb, p, u_begin, u_end, iters;
+    uint32_t *out_count, *out_words;
+    uint32_t cap;
+    PowFillDev fx;
+    uint32_t claim;
+    uint32_t* counter;
+};
+template <bool RANGE>
+__global__ __launch_bounds__(256, 7) void pow_search_claim_kernel(PowJobDev job, uint32_t vb, uint32_t p, uint32_t u_begin,
+                                                                  uint32_t u_end, uint32_t iters,
+                                                                  uint32_t* __restrict__ out_count,
+                                                                  uint32_t* __restrict__ out_words, uint32_t cap,
+                                                                  PowFillDev fx, uint32_t claim, uint32_t* counter) {
+    const uint32_t lane = threadIdx.x & 63u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    for (;;) {
+        auto ka = (__attribute__((address_space(4))) const PowClaimKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const uint32_t step = ka->claim, n_u = ka->u_end - ka->u_begin;
+        uint32_t taken = 0;
+        if (lane == 0) taken = __hip_atomic_fetch_add(ka->counter, step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        taken = __builtin_amdgcn_readfirstlane(taken);
+        if (taken >= n_u) return;
+        uint32_t u = ka->u_begin + taken;
+        const uint32_t u_stop = n_u - taken < step ? ka->u_end : u + step;
+        PowSplitCacheT<true> cached;
+        PowSplitLane lc;
+        pow_split_prologue(job, p, vb + u, lane, cached, lc);
+        cached.next = __builtin_amdgcn_readfirstlane(cached.next);  // see pow_a_fill
+        for (; u < u_stop; ++u) {
+            const uint32_t sv = vb + u;
+            const uint32_t a = pow_a_fill<2>(job, p, sv, lane, cached, lc, fx, RANGE);
+            bool hit;
+            if (RANGE) {
+                hit = a < job.range_width;
+            } else {
+                const uint32_t h0 = job.mid[0] + a;
+                hit = ((h0 ^ job.tword) & job.tmask) == 0 && ((h0 >> job.frac_shift) & 0xfu) < job.frac_limit;
+            }
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(hit) != 0, 0)) {
+                if (hit) {
+                    const uint32_t slot = atomicAdd(out_count, 1u);
+                    if (slot < cap) out_words[slot] = sv + lc.lanep;
+                }
+            }
+        }
+    }
+#endif
+}
+// Keep PowClaimKernArgs and the kernel's parameter list in step: the kernel argument segment holds the arguments in
+// order, each at its own alignment, and the checks below compute that layout from the kernel's signature. A
+// parameter added, removed, retyped or moved without the same change to the struct does not compile.
+template <class F>
+struct PowKernargLayout;
+template <class... A>
+struct PowKernargLayout<void (*)(A...)> {
+    static constexpr size_t kCount = sizeof...(A);
+    static constexpr size_t offset(size_t index) {  // of argument `index`; index == kCount: the segment's size
+        constexpr size_t size[] = {sizeof(A)...}, align[] = {alignof(A)...};
+        size_t at = 0;
+        for (size_t i = 0; i < kCount; ++i) {
+            at = (at + align[i] - 1) / align[i] * align[i];
+            if (i == index) return at;
+            at += size[i];
+        }
+        return at;
+    }
+};
+using PowClaimLayout = PowKernargLayout<decltype(&pow_search_claim_kernel<true>)>;
+static_assert(std::is_same_v<decltype(&pow_search_claim_kernel<true>), decltype(&pow_search_claim_kernel<false>)>);
+static_assert(PowClaimLayout::kCount == 12 && std::is_standard_layout_v<PowClaimKernArgs>);
+static_assert(offsetof(PowClaimKernArgs, job) == PowClaimLayout::offset(0) && offsetof(PowClaimKernArgs, vb) == PowClaimLayout::offset(1) &&
+              offsetof(PowClaimKernArgs, p) == PowClaimLayout::offset(2) && offsetof(PowClaimKernArgs, u_begin) == PowClaimLayout::offset(3) &&
+              offsetof(PowClaimKernArgs, u_end) == PowClaimLayout::offset(4) && offsetof(PowClaimKernArgs, iters) == PowClaimLayout::offset(5) &&
+              offsetof(PowClaimKernArgs, out_count) == PowClaimLayout::offset(6) && offsetof(PowClaimKernArgs, out_words) == PowClaimLayout::offset(7) &&
+              offsetof(PowClaimKernArgs, cap) == PowClaimLayout::offset(8) && offsetof(PowClaimKernArgs, fx) == PowClaimLayout::offset(9) &&
+              offsetof(PowClaimKernArgs, claim) == PowClaimLayout::offset(10) && offsetof(PowClaimKernArgs, counter) == PowClaimLayout::offset(11),
+              "PowClaimKernArgs must mirror pow_search_claim_kernel's parameters");
+static_assert(offsetof(PowClaimKernArgs, u_begin) == 456 && offsetof(PowClaimKernArgs, claim) == 504 &&
+              offsetof(PowClaimKernArgs, counter) == 512, "the offsets in the code object's metadata (.args) at the time of writing");
+
 template <bool RANGE>
 __global__ __launch_bounds__(256, 8) void pow_search_split_kernel(PowJobDev job, uint32_t vb, uint32_t p, uint32_t u_begin,
                                                                   uint32_t u_end, uint32_t iters,
@@ -1279,8 +1379,9 @@ std::vector<uint32_t> pow_split_wave_host(const PowJobHost& hj, uint32_t vb, uin
                                           uint32_t iters, int variant) {
     if (hj.header.size() != 108) throw std::invalid_argument("the split kernel is for the 108-byte header");
     if (p > uint32_t(kPowSplitMaxLog2)) throw std::invalid_argument("p must be at most 26: the lane index takes six bits");
-    if (variant == 0) variant = 11;  // kPowDefaultVariant, checked below
-    if (variant != 10 && variant != 11) throw std::invalid_argument("the wave loop is variant 10's and variant 11's");
+    if (variant == 0) variant = 12;  // kPowDefaultVariant, checked below
+    if (variant == 12) variant = 11;  // the claiming kernel runs variant 11's wave loop
+    if (variant != 10 && variant != 11) throw std::invalid_argument("the wave loop is variant 10's, 11's and 12's");
     const PowJobDev job = make_pow_job(hj);
     return variant == 11 ? pow_split_wave_loop<true>(job, vb, p, u_first, iters)
                          : pow_split_wave_loop<false>(job, vb, p, u_first, iters);
@@ -1302,9 +1403,12 @@ uint32_t pow_job_h0_host(const PowJobHost& hj, uint32_t v) {
     return hj.header.size() == 108 ? pow_h0_pre<2>(job, v) : pow_h0_pre<1>(job, v);
 }
 
+// Claim counters of variant 12, one per dispatch of a search: they lie behind the hit count in one allocation, so
+// that the memset at the start of a search zeroes both.
+constexpr uint32_t kPowClaimCounters = 63;
 struct PowDeviceBuffers {
     int device = -1;
-    uint32_t* d_count = nullptr;
+    uint32_t* d_count = nullptr;   // the hit count, then kPowClaimCounters claim counters
     uint32_t* d_words = nullptr;
     uint32_t cap = 0;
 };
@@ -1317,7 +1421,7 @@ static PowDeviceBuffers& pow_buffers(uint32_t cap) {
     PowDeviceBuffers& b = g_pow_bufs;
     if (b.device != dev || b.cap < cap) {
         if (b.d_count) { (void)hipFree(b.d_count); (void)hipFree(b.d_words); }
-        hip_check(hipMalloc(&b.d_count, sizeof(uint32_t)), "hipMalloc count");
+        hip_check(hipMalloc(&b.d_count, sizeof(uint32_t) * (1 + kPowClaimCounters)), "hipMalloc count");
         hip_check(hipMalloc(&b.d_words, sizeof(uint32_t) * cap), "hipMalloc words");
         b.device = dev;
         b.cap = cap;
@@ -1343,12 +1447,21 @@ static PowDeviceBuffers& pow_buffers(uint32_t cap) {
 //  11  variant 10 with one scalar or sequencer instruction in front of every slow instruction (pow_a_fill,
 //     pow_search_fill_kernel): each K loaded in the slot in front of its add3, rounds 12 and 13 pinned, the nonce
 //     word and W17 not materialised, the range check's base folded into round 63's K
-constexpr int kPowDefaultVariant = 11;
+//  12  variant 11's loop under a claiming wave loop (pow_search_claim_kernel): a wave takes `claim` values of U at a
+//     time from a counter until the dispatch's range is used up, so no SIMD drains before the dispatch ends; a piece
+//     is one dispatch unless chunk_iters, UPOW_POW_DISPATCH_LOG2 or a live node stream says otherwise
+constexpr int kPowDefaultVariant = 12;
 constexpr int kPowSplitVariant = 10;
 constexpr int kPowFillVariant = 11;
-constexpr int kPowVariantCount = 12;
-static_assert(kPowDefaultVariant == 11, "pow_split_wave_host resolves 0 to the default variant by its number");
-static bool pow_is_split(int variant) { return variant == kPowSplitVariant || variant == kPowFillVariant; }
+constexpr int kPowClaimVariant = 12;
+constexpr int kPowVariantCount = 13;
+// Values of U a wave claims at a time where the caller names none: the best of 8..128 over a 2^32 sweep, where 16 to
+// 64 are within 0.2 % of one another (docs/PERF.md, "PoW claimed chunks")
+constexpr uint32_t kPowClaimDefault = 32;
+static_assert(kPowDefaultVariant == 12, "pow_split_wave_host resolves 0 to the default variant by its number");
+static bool pow_is_split(int variant) {
+    return variant == kPowSplitVariant || variant == kPowFillVariant || variant == kPowClaimVariant;
+}
 
 using PowKernelFn = void (*)(PowJobDev, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t);
 
@@ -1390,7 +1503,7 @@ uint32_t pow_job_h0_host(const PowJobHost& hj, uint32_t v, int variant) {
         case 8: return pow_h0_sched<2, 2, false, 1>(job, v);
         case 9: return pow_h0_sched<2, 2, false, 2>(job, v);
         case 10: return pow_h0_split<false>(job, v);
-        case 11: return pow_h0_split<true>(job, v);
+        case 11: case 12: return pow_h0_split<true>(job, v);
         default: return pow_h0_pre<2>(job, v);
     }
 }
@@ -1402,7 +1515,8 @@ static int pow_resident_blocks(bool v2, int variant) {
     hip_check(hipGetDevice(&dev), "hipGetDevice");
     hip_check(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev), "attr");
     const int rv = pow_resolve_variant(variant);
-    const void* fn = v2 && rv == kPowFillVariant    ? reinterpret_cast<const void*>(&pow_search_fill_kernel<true>)
+    const void* fn = v2 && rv == kPowClaimVariant   ? reinterpret_cast<const void*>(&pow_search_claim_kernel<true>)
+                     : v2 && rv == kPowFillVariant  ? reinterpret_cast<const void*>(&pow_search_fill_kernel<true>)
                      : v2 && rv == kPowSplitVariant ? reinterpret_cast<const void*>(&pow_search_split_kernel<true>)
                                                     : reinterpret_cast<const void*>(pow_kernel_fn(v2, variant));
     hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, 0), "occupancy");
@@ -1424,23 +1538,30 @@ PowKernelInfo pow_kernel_info(int variant) {
 // Search nonce words [start, start + count) (count a multiple of the grid size is not required:
 // the tail is covered by an extra short launch). Returns all candidate nonce words (host re-checks).
 PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, int grid_blocks,
-                         uint32_t chunk_iters, uint32_t cap, int variant) {
+                         uint32_t chunk_iters, uint32_t cap, int variant, uint32_t claim) {
     PowJobDev job = make_pow_job(hj);
     const bool v2 = hj.header.size() == 108;
     const PowKernelFn kernel = pow_kernel_fn(v2, variant);
     node_device_enter();  // a rank's search from any of its threads runs on the rank's own GPU
     PowDeviceBuffers& buf = pow_buffers(cap);
     hipStream_t st = miner_stream();  // least priority: node kernels go first (csrc/streams.h)
-    hip_check(hipMemsetAsync(buf.d_count, 0, sizeof(uint32_t), st), "memset");
+    const bool claiming = v2 && pow_resolve_variant(variant) == kPowClaimVariant;
+    hip_check(hipMemsetAsync(buf.d_count, 0, sizeof(uint32_t) * (claiming ? 1 + kPowClaimCounters : 1), st), "memset");
     const uint32_t block = 256;
     if (grid_blocks <= 0) grid_blocks = pow_resident_blocks(v2, variant);
     const uint64_t per_launch_threads = uint64_t(grid_blocks) * block;
+    bool whole_pieces = false;
     if (chunk_iters == 0) {
         // nonces per dispatch: 2^28 (~7.6 ms on MI355X) for a dedicated miner; 2^23 (~0.25 ms) once this
         // process also runs node kernels, so a queued node kernel waits at most one short dispatch (the miner
-        // CLI next to a node process uses 2^23 too); UPOW_POW_DISPATCH_LOG2 overrides both
-        int lg = node_stream_live().load() ? 23 : 28;
-        if (const char* e = std::getenv("UPOW_POW_DISPATCH_LOG2")) lg = std::max(16, std::min(32, std::atoi(e)));
+        // CLI next to a node process uses 2^23 too); UPOW_POW_DISPATCH_LOG2 overrides both.
+        // Variant 12 as a dedicated miner: a piece is one dispatch. Every dispatch of claiming waves still ends in a
+        // drain of up to one claim per wave, which sixteen times a sweep costs more than claiming gains.
+        const bool node = node_stream_live().load();
+        int lg = node ? 23 : 28;
+        const char* e = std::getenv("UPOW_POW_DISPATCH_LOG2");
+        if (e) lg = std::max(16, std::min(32, std::atoi(e)));
+        whole_pieces = claiming && !node && !e;
         chunk_iters = uint32_t(std::max<uint64_t>(1, (uint64_t(1) << lg) / per_launch_threads));
     }
     uint64_t done = 0;
@@ -1449,6 +1570,12 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
         // dispatch and iterations (values of U) per wave per dispatch. A piece smaller than a dispatch is spread
         // over as many waves as it has iterations for.
         const bool fill = pow_resolve_variant(variant) == kPowFillVariant;
+        const auto claimed = job.range_ok ? &pow_search_claim_kernel<true> : &pow_search_claim_kernel<false>;
+        // a claim that the caller names stands; UPOW_POW_CLAIM takes the place of the automatic value only
+        if (claiming && claim == 0) {
+            if (const char* e = std::getenv("UPOW_POW_CLAIM")) claim = uint32_t(std::max(0, std::atoi(e)));
+        }
+        uint32_t dispatches = 0;
         const auto split = job.range_ok ? &pow_search_split_kernel<true> : &pow_search_split_kernel<false>;
         const auto filled = job.range_ok ? &pow_search_fill_kernel<true> : &pow_search_fill_kernel<false>;
         const PowFillDev fx = make_pow_fill(job);
@@ -1459,11 +1586,26 @@ PowResult pow_search_gpu(const PowJobHost& hj, uint64_t start, uint64_t count, i
             const uint32_t vb = uint32_t(start + done), n_u = uint32_t(1) << p;
             for (uint32_t u = 0; u < n_u;) {
                 const uint32_t left = n_u - u;
-                const uint32_t iters = uint32_t(std::min<uint64_t>(chunk_iters, (left + waves - 1) / waves));
+                const uint32_t iters = uint32_t(std::min<uint64_t>(whole_pieces ? left : chunk_iters, (left + waves - 1) / waves));
                 const uint64_t need = (uint64_t(left) + iters - 1) / iters;  // waves that have an iteration
                 const uint32_t gb = uint32_t(std::min<uint64_t>(uint64_t(grid_blocks), (need + 3) / 4));
                 const uint32_t u_end = uint32_t(std::min<uint64_t>(n_u, u + uint64_t(gb) * 4 * iters));
-                if (fill)
+                if (claiming) {
+                    // Automatic: never more than a quarter of a wave's share, so that no resident wave is left
+                    // without work because the claims are too coarse. Any claim: at most the range, and small
+                    // enough that the counter, which every wave pushes once past the range, does not wrap.
+                    const uint32_t n = u_end - u;
+                    uint32_t c = claim ? claim : std::min(kPowClaimDefault, std::max(1u, iters / 4));
+                    c = uint32_t(std::min<uint64_t>(std::min(c, n), (0xffffffffull - n) / (uint64_t(gb) * 4 + 1)));
+                    c = std::max(c, 1u);
+                    // a counter of its own for each dispatch; when they are used up, zero them again behind the
+                    // dispatches that used them
+                    const uint32_t k = dispatches++ % kPowClaimCounters;
+                    if (k == 0 && dispatches > 1)
+                        hip_check(hipMemsetAsync(buf.d_count + 1, 0, sizeof(uint32_t) * kPowClaimCounters, st), "memset claims");
+                    hipLaunchKernelGGL(claimed, dim3(gb), dim3(block), 0, st, job, vb, p, u, u_end, iters, buf.d_count,
+                                       buf.d_words, cap, fx, c, buf.d_count + 1 + k);
+                } else if (fill)
                     hipLaunchKernelGGL(filled, dim3(gb), dim3(block), 0, st, job, vb, p, u, u_end, iters, buf.d_count,
                                        buf.d_words, cap, fx);
                 else

@@ -114,7 +114,8 @@ def loop_bodies(asm: str) -> dict:
         stats = asm[end:end + 6000]
         vg = re.search(r'; NumVgprs: (\d+)', stats)
         occ = re.search(r'; Occupancy: (\d+)', stats)
-        hdr = re.search(r'^(\.LBB\w+):\s*; =>This Inner Loop Header', body, re.M)
+        # variant 12's loop lies in the claiming loop: its header line names the parent first
+        hdr = re.search(r'^(\.LBB\w+):\s*;(?:\s*Parent Loop[^\n]*\n\s*;)? =>\s*This Inner Loop Header', body, re.M)
         if not hdr:
             continue
         loop = body[hdr.end():]

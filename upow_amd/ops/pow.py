@@ -67,15 +67,19 @@ class PowSearchResult:
 
 def search(job: PowJob, start: int = 0, count: int = NONCE_SPACE, device: Optional[str] = None,
            threads: Optional[int] = None, grid_blocks: int = 0, chunk_iters: int = 0,
-           cap: int = 1 << 16, variant: int = 0) -> PowSearchResult:
-    """Search nonce *words* [start, start+count). ``device`` = 'gpu' | 'cpu' | None (auto)."""
+           cap: int = 1 << 16, variant: int = 0, claim: int = 0) -> PowSearchResult:
+    """Search nonce *words* [start, start+count). ``device`` = 'gpu' | 'cpu' | None (auto).
+
+    ``claim``: values of U a wave of kernel variant 12 takes from its dispatch's counter at a time; 0 leaves the
+    choice to the native side (``UPOW_POW_CLAIM``, or its own default)."""
     L = lib()
     if device is None:
         device = 'gpu' if gpu_available() else 'cpu'
     t0 = time.perf_counter()
     if device == 'gpu':
+        # named only where set: a build from before variant 12, loaded for an A/B, has no such argument
         searched, hits, words = L.pow_search_gpu(*job.native_args(), start, count, grid_blocks, chunk_iters,
-                                                 cap, variant)
+                                                 cap, variant, **({'claim': claim} if claim else {}))
     else:
         searched, hits, words = L.pow_search_host(*job.native_args(), start, count,
                                                   threads or max(1, os.cpu_count() or 1))
